@@ -40,9 +40,14 @@ install() every arithmetic name it resolves is this library's; its own arithmeti
 GPU tensors, and the line reports `via_install.oracle_imported_by_the_timed_path` (false) and the kernels of a step (all `fm::`).
 
 Prints ONE JSON line (rank 0) with `roofline` for the fused flow kernel (HIP events on its launch stream
-inside the timed region), `roofline_tracking` when the tracking loss runs (track_pairs: VALU-bound, GFLOP/s)
-and, at N = 1, `cpu_baseline` (the oracle — a PyTorch-CPU port of the reference path — timed on a bounded
-sample of the same workload).
+inside the timed region) and `roofline_tracking` when the tracking loss runs (track_pairs: VALU-bound, GFLOP/s).
+A plain run does only that: set-up, W warm-up steps, K timed steps, the line.  `--full` adds the legs that measure or
+check beyond the headline, after the timed steps: at N = 1 `cpu_baseline` (the oracle — a PyTorch-CPU port of the
+reference path — timed on a bounded sample of the same workload), `sustained`, the hand-built twin (`via_install.direct`),
+the launch count of a step, the `ate` legs and `default_resolution` on the headline config, and `quoted_records`.
+
+    python bench.py --full                             # the headline line plus every leg above
+    python bench.py --dump-outputs DIR                 # also writes the last timed step's loss and gradients as DIR/<name>.npy
 """
 
 from __future__ import annotations
@@ -78,8 +83,15 @@ CONFIGS = {
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs a plain run leaves out: the CPU baseline, the sustained steps, the hand-built twin, "
+                         "the launch count, the ATE legs and the default-resolution children (each where its `auto` applies), quoted records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed — its loss, the parameters' gradients and, with an optimiser, the updated parameters — as "
+                         "DIR/<name>.npy (float32; arrays above 2^21 elements as a fixed, seeded sample of 2^21 of them, flattened; rank 0's shard "
+                         "in a multi-rank run)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c1")
     ap.add_argument("--scaling", choices=["strong", "weak"], default=None, help="default: the config's (strong for c1-c3, weak for c4)")
     ap.add_argument("--inputs", choices=["scene", "iid"], default=None, help="default: the config's (scene for c1-c3, iid for c4)")
@@ -90,9 +102,9 @@ def parse():
     ap.add_argument("--points", type=int, default=1000,
                     help="Procrustes points (config/model/extrinsics/procrustes.yaml:3); 0 = all pixels (ablation_explicit_depth.yaml:11-12)")
     ap.add_argument("--cpu-frames", type=int, default=-1,
-                    help="frames of the CPU-baseline leg, taken from the front of the SAME inputs the GPU leg runs on (0 = skip; default: the whole "
-                         "video when the host has >= 96 GB of free memory — one iteration of 150 x 720p takes the oracle ~40 GB and ~30 s — "
-                         "else a 32-frame sample, labelled as such)")
+                    help="frames of the CPU-baseline leg, taken from the front of the SAME inputs the GPU leg runs on (0 = skip; default: skip without "
+                         "--full, with it the whole video when the host has >= 96 GB of free memory — one iteration of 150 x 720p takes the oracle ~40 GB "
+                         "and ~30 s — else a 32-frame sample, labelled as such)")
     ap.add_argument("--cpu-iters", type=int, default=3, help="timed iterations of the CPU-baseline leg after its warm-up (BASELINE.md §3: 1 warm-up + 3)")
     ap.add_argument("--cpu-threads", type=int, default=16,
                     help="torch threads for the CPU baseline (16 measured fastest on the 256-thread EPYC 9575F host: "
@@ -121,10 +133,10 @@ def parse():
                          "one-rank RCCL communicator): the per-rank step time of a K-GPU run without the wire time")
     ap.add_argument("--share-rank", type=int, default=-1, help="which rank's share (default: an interior rank with the largest share)")
     ap.add_argument("--count-launches", action="store_true", help="count the kernel launches of one step with torch.profiler (after the timed region)")
-    ap.add_argument("--sustained-steps", type=int, default=100,
+    ap.add_argument("--sustained-steps", type=int, default=None,
                     help="N = 1: after the timed K steps, N more steps timed separately and reported as `sustained` (informational; `value` stays the K steps "
                          "after W warm-up steps).  The first ~30 launches after an idle period run on a power-management transient (profiles/r04_driver_command_ramp.txt): "
-                         "a 20-step run measures that transient, a 2000-step overfit run the sustained state.  0 = skip")
+                         "a 20-step run measures that transient, a 2000-step overfit run the sustained state.  0 = skip; default: 100 with --full, else 0")
     ap.add_argument("--whole", action="store_true",
                     help="config c4 WHOLE on one GPU: all 1200 frames @ 1080x1920 (79.6 GB of inputs + a 59.7 GB packed copy of the 288 GB) instead of "
                          "one GPU's 150-frame shard; implies --release-originals")
@@ -138,7 +150,7 @@ def parse():
                     help="the metric's second half, `final ATE vs ref`, MEASURED BY THIS RUN: after the timed region, the optimisation the imported reference "
                          "ran once on the build container's CPU (oracle/make_ate_reference.py -> tests/golden/ate_*_imported_reference.json: 150 frames, flow + "
                          "tracking, softmin -> regressed intrinsics, Adam) is run here by flowmap_amd from the same initial parameters on the same seeded scene, and "
-                         "both ATEs go into the line's `ate` block.  auto: at N = 1 on the headline config when a fixture is present (seconds on the GPU)")
+                         "both ATEs go into the line's `ate` block.  auto: with --full, at N = 1 on the headline config when a fixture is present (seconds on the GPU)")
     ap.add_argument("--ate-fixture", default=None, help="the reference leg's record (default: the 720p one under tests/golden/, else the 360p one)")
     ap.add_argument("--model", choices=["installed", "direct"], default="installed",
                     help="how the step's modules are built.  `installed` (default): flowmap_amd.install() patches a reference-LAYOUT `flowmap` package "
@@ -152,7 +164,7 @@ def parse():
     ap.add_argument("--default-resolution", choices=["auto", "on", "off"], default="auto",
                     help="the reference's default operating point (config/overfit.yaml:33-38: 150 frames of ~180x240, flow + tracking) beside the headline: "
                          "two child runs of this file — the package's ModelWrapperOverfit.training_step eager and under install(graph=True) — reported "
-                         "under `default_resolution` (auto: with the default headline run on one GPU, like the ATE leg)")
+                         "under `default_resolution` (auto: with --full, on the default headline run on one GPU, like the ATE leg)")
     ap.add_argument("--backend", choices=["auto", "nccl", "gloo"], default="auto",
                     help="the process group's backend: auto = nccl (RCCL) on GPUs, gloo on the CPU dry run.  `gloo` on GPUs (it moves GPU tensors through the "
                          "host) is an alternative for --one-gpu")
@@ -163,7 +175,12 @@ def parse():
     ap.add_argument("--torch-baseline", type=int, default=0, metavar="STEPS",
                     help="after the timed region: the reference's op sequence on stock PyTorch-ROCm on this GPU (tests/tools/torch_gpu_reference_ops.py "
                          "in a process of its own, 1 warm-up + STEPS steps on i.i.d. inputs of the workload's size) as `rocm_torch_baseline`")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.sustained_steps is None:
+        args.sustained_steps = 100 if args.full else 0
+    return args
 
 
 # --------------------------------------------------------------------------------------
@@ -464,9 +481,12 @@ def c0_ate_fixture():
 
 def _cpu_frames(args, f_video, h, w):
     """Frames of the CPU-baseline leg: the whole video when it is no bigger than 1.25 x the headline workload and the host has the memory
-    (one iteration of 150 x 720p takes the oracle ~40 GB and ~25 s), else a 32-frame sample from the front of the same inputs."""
+    (one iteration of 150 x 720p takes the oracle ~40 GB and ~25 s), else a 32-frame sample from the front of the same inputs.
+    Without --full the default is no CPU leg."""
     if args.cpu_frames >= 0:
         return min(args.cpu_frames, f_video)
+    if not args.full:
+        return 0
     try:
         avail_gb = int(next(line for line in open("/proc/meminfo") if line.startswith("MemAvailable")).split()[1]) / 2**20
     except Exception:  # noqa: BLE001
@@ -490,6 +510,33 @@ def count_launches(step, device):
         return None, [f"torch.profiler failed: {exc}"]
 
 
+DUMP_SAMPLE = 2**21  # elements written of a larger array: four 150 x 720p ones (gradients + parameters with an optimiser) stay at 32 MiB
+
+
+def dump_outputs(out_dir, loss, model, optimizer):
+    """--dump-outputs: what the last timed step handed its caller — the loss, every parameter's gradient and, when an optimiser stepped, the
+    parameters — as <out_dir>/<name>.npy, float32 (float64 stays float64).  An array of more than DUMP_SAMPLE elements is written as its
+    flattened values at DUMP_SAMPLE indices drawn by a generator seeded with its size (sorted, repeats dropped): the same in every run."""
+    import numpy as np
+
+    arrays = {"loss": torch.tensor(loss.item(), dtype=torch.float32)}
+    for name, p in model.named_parameters():
+        if p.grad is not None:
+            arrays[f"grad_{name}"] = p.grad
+        if optimizer is not None:
+            arrays[f"param_{name}"] = p
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(t.numel()).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        np.save(out / f"{name.replace('.', '_')}.npy", a if a.dtype == np.float64 else a.astype(np.float32))
+    print(f"[bench] wrote {len(arrays)} arrays of the last timed step to {out}", file=sys.stderr)
+
+
 def _reserve_stdout():
     """The driver reads ONE JSON line from stdout, but RCCL prints a version banner to the C-level
     stdout (fd 1) when the communicator comes up.  Keep a private handle on the real stdout for the
@@ -509,11 +556,14 @@ def _free_port() -> int:
 
 
 def launch_ranks(args):
-    """`python bench.py --gpus N` with N > 1 and no launcher around it: become `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
+    """`python bench.py --gpus N` with N > 1 and no launcher around it: run `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
     --master-addr 127.0.0.1 --master-port <free> bench.py <the same arguments>` — one process per GPU over RCCL, rank 0 prints the ONE JSON
     line — like the reference, which goes multi-GPU without a launcher (overfit.py:94-108: Lightning spawns when device_count() > 1).  The
-    process image is replaced (exec): exit code, signals and stdout are the launcher's.  FLOWMAP_BENCH_LAUNCHER names the script the ranks
+    launcher is a child process (this one may have initialised the GPU runtime to count the devices, so it is not replaced by exec); its exit
+    code becomes this process's and the ranks share its stdout.  FLOWMAP_BENCH_LAUNCHER names the script the ranks
     run instead of this file (tests/test_bench_dryrun.py: the launcher that injects the host test double for the gloo dry run)."""
+    import subprocess
+
     on_gpu = os.environ.get("FLOWMAP_BENCH_DEVICE", "cuda") == "cuda"
     if on_gpu and not args.one_gpu:
         visible = torch.cuda.device_count()
@@ -527,7 +577,7 @@ def launch_ranks(args):
     env.setdefault("OMP_NUM_THREADS", "8")  # (torch.distributed.run would set 1 and warn; the ranks' host work is launch glue)
     print(f"[bench] --gpus {args.gpus}: launching {args.gpus} ranks: {' '.join(cmd)}", file=sys.stderr, flush=True)
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 def main():
@@ -535,7 +585,7 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         if args.share:
             raise SystemExit("--share K runs one rank's share on ONE process: --gpus 1")
-        launch_ranks(args)  # (does not return)
+        launch_ranks(args)  # (does not return: exits with the launcher's status)
     result_stream = _reserve_stdout()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
@@ -887,6 +937,8 @@ def main():
         tmax = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:  # (before any later leg runs a step and overwrites the gradients)
+        dump_outputs(args.dump_outputs, loss, model, optimizer)
 
     flow_ms = _ops.flow_kernel_times() if not args.graph else eager_flow_ms
     track_ms = _ops.flow_kernel_times(tracking=True)
@@ -905,7 +957,7 @@ def main():
                              "which at K = 20, W = 5 lie on the power-management transient of a GPU that was idle (kernel_ms_per_launch shows it)"}
     _ops.flow_kernel_timing(False)
     direct = None
-    if package is not None and world == 1 and args.share <= 1 and not args.graph and optimizer is None and not args.release_originals:
+    if args.full and package is not None and world == 1 and args.share <= 1 and not args.graph and optimizer is None and not args.release_originals:
         # the same step with this package's own Model and loss classes constructed by hand (what rounds 1-4 timed), on the same parameters and inputs,
         # straight after the steps above: the drop-in path must cost what the hand-built one costs
         direct_model, direct_fns = direct_modules()
@@ -954,7 +1006,8 @@ def main():
     achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
     launches, launch_names = (None, [])
     under_rocprof = any("rocprof" in os.environ.get(k, "").lower() for k in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB", "ROCPROFILER_LIBRARY_CTOR"))
-    if on_gpu and rank == 0 and (args.count_launches or (world == 1 and not args.graph and not under_rocprof and not os.environ.get("FLOWMAP_BENCH_NO_PROFILER"))):
+    if on_gpu and rank == 0 and (args.count_launches or (args.full and world == 1 and not args.graph and not under_rocprof
+                                                         and not os.environ.get("FLOWMAP_BENCH_NO_PROFILER"))):
         launches, launch_names = count_launches(step, device)  # (two tracers in one process do not mix: skipped under rocprofv3)
 
     if rank == 0:
@@ -1036,7 +1089,7 @@ def main():
         # the metric's second half ("final ATE vs ref"), measured by THIS run (ate_leg above); records of earlier runs are quoted under
         # `quoted_records`, never beside the measured values
         fixture = Path(args.ate_fixture) if args.ate_fixture else default_ate_fixture()
-        want_ate = args.ate == "on" or (args.ate == "auto" and world == 1 and args.share <= 1 and on_gpu and args.config == "c1" and not args.whole
+        want_ate = args.ate == "on" or (args.ate == "auto" and args.full and world == 1 and args.share <= 1 and on_gpu and args.config == "c1" and not args.whole
                                         and (f_video, h, w) == (150, 720, 1280) and tracks is None and optimizer is None and not args.graph
                                         and not under_rocprof)
         if want_ate and fixture is not None and fixture.exists():
@@ -1051,15 +1104,16 @@ def main():
                 result["ate_c0_full_schedule"] = ate_leg(device, c0_ate_fixture())
             except Exception as exc:  # noqa: BLE001
                 result["ate_c0_full_schedule"] = {"measured_by_this_run": False, "failed": repr(exc)[:400]}
-        if args.default_resolution == "on" or (args.default_resolution == "auto" and want_ate and wrapper is None):
+        if args.default_resolution == "on" or (args.default_resolution == "auto" and args.full and want_ate and wrapper is None):
             result["default_resolution"] = default_resolution_leg()
-        quoted = {}
-        try:
-            rec = json.loads((ROOT / "profiles" / "r04_ate_150x360x640_vs_imported_reference.json").read_text())
-            quoted["ate_150x360x640_round4"] = {"record": "profiles/r04_ate_150x360x640_vs_imported_reference.json", "ate_reference": rec["ate_reference_path_cpu"],
-                                                "ate_flowmap_amd": rec["ate_flowmap_amd"], "note": "200 Adam steps at lr 1e-3, measured in round 4, not by this run"}
-        except Exception:  # noqa: BLE001
-            pass
+        quoted = {}  # (records of earlier runs: --full only)
+        if args.full:
+            try:
+                rec = json.loads((ROOT / "profiles" / "r04_ate_150x360x640_vs_imported_reference.json").read_text())
+                quoted["ate_150x360x640_round4"] = {"record": "profiles/r04_ate_150x360x640_vs_imported_reference.json", "ate_reference": rec["ate_reference_path_cpu"],
+                                                    "ate_flowmap_amd": rec["ate_flowmap_amd"], "note": "200 Adam steps at lr 1e-3, measured in round 4, not by this run"}
+            except Exception:  # noqa: BLE001
+                pass
         if package is not None:
             result["via_install"] = {
                 "package": package[0], "package_path": package[1],
@@ -1073,8 +1127,8 @@ def main():
                 "ms_per_step": ms_per_step, "launches_per_step": launches,
                 # every kernel of a step is this library's (a torch kernel here would mean some name fell through to eager arithmetic), and the
                 # oracle had not been imported when the timed steps ended
-                "kernels_not_from_libflowmap_hip": [k for k in launch_names if "fm::" not in k and not k.startswith(("softmin_", "random_"))
-                                                    and "#" not in k],
+                "kernels_not_from_libflowmap_hip": None if launches is None else [k for k in launch_names if "fm::" not in k
+                                                                                  and not k.startswith(("softmin_", "random_")) and "#" not in k],
                 "oracle_imported_by_the_timed_path": oracle_loaded_by_product_path,
                 "sustained_ms_per_step": sustained["ms_per_step"] if sustained is not None else None,
                 "training_step": None if wrapper is None else {
@@ -1161,7 +1215,7 @@ def main():
             }
         if args.torch_baseline > 0 and on_gpu and world == 1:
             result["rocm_torch_baseline"] = torch_baseline(f_video, h, w, args.points, args.torch_baseline)
-        elif (f_video, h, w, args.points) == (150, 720, 1280, 1000) and tracks is None and optimizer is None:
+        elif args.full and (f_video, h, w, args.points) == (150, 720, 1280, 1000) and tracks is None and optimizer is None:
             # (measured once, not by this run — like `ate`: the reference's op sequence on stock PyTorch-ROCm takes 20 s per step)
             record = ROOT / "profiles" / "r04_stock_pytorch_rocm_150_frames_in_16_frame_windows.json"
             try:

@@ -40,7 +40,7 @@ def _run(world: int, extra):
 
 @pytest.mark.parametrize("extra", [["--config", "c1"], ["--config", "c2"], ["--config", "c1", "--intrinsics", "softmin"]], ids=["flow", "flow+tracking", "softmin"])
 def test_strong_scaling_reports_the_whole_video(extra):
-    single = _run(1, extra)
+    single = _run(1, [*extra, "--full"])  # (--full: the hand-built twin, `via_install.direct`)
     assert single["n_gpus"] == 1 and single["config"]["frames_per_gpu"] == 9
     # the default line is measured on the drop-in path: the stand-in package's Model / get_losses after install(); the hand-built modules agree
     via = single["via_install"]
@@ -74,6 +74,44 @@ def test_weak_scaling_runs_one_video_per_rank():
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["config"]["frames_per_gpu"] == 9
 
 
+def test_plain_run_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """A plain run prints the headline line without the --full legs; --dump-outputs DIR writes the last timed step's loss and gradients
+    as float32 .npy files, and two runs with the same arguments write the same arrays."""
+    import numpy as np
+
+    lines = [_run(1, ["--config", "c1", "--dump-outputs", str(tmp_path / run)]) for run in ("a", "b")]
+    line = lines[0]
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert "quoted_records" not in line and "sustained" not in line and line["via_install"]["direct"] is None
+    names = sorted(p.name for p in (tmp_path / "a").glob("*.npy"))
+    assert names == ["grad_backbone_depth.npy", "grad_backbone_weights.npy", "grad_intrinsics_focal_length.npy", "loss.npy"]
+    assert names == sorted(p.name for p in (tmp_path / "b").glob("*.npy"))
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float32 and a.shape == b.shape
+        np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-6 * float(np.abs(b).max()), err_msg=name)
+    assert np.load(tmp_path / "a" / "grad_backbone_depth.npy").shape == (9, 24, 32)
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy")) - line["config"]["loss"]) <= 1e-6 * abs(line["config"]["loss"])
+
+
+def test_dump_outputs_samples_a_large_array_the_same_way_every_time(tmp_path):
+    """An output above bench.DUMP_SAMPLE elements is written as a fixed, seeded sample of its values."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    model = torch.nn.Module()
+    model.big = torch.nn.Parameter(torch.zeros(bench.DUMP_SAMPLE + 5))
+    model.big.grad = torch.arange(bench.DUMP_SAMPLE + 5, dtype=torch.float32)
+    for run in ("a", "b"):
+        bench.dump_outputs(tmp_path / run, torch.tensor(1.5), model, None)
+    a, b = np.load(tmp_path / "a" / "grad_big.npy"), np.load(tmp_path / "b" / "grad_big.npy")
+    assert a.dtype == np.float32 and 0.5 * bench.DUMP_SAMPLE < a.size <= bench.DUMP_SAMPLE
+    assert np.array_equal(a, b) and np.all(np.diff(a) > 0)  # (the values ARE their indices here: sorted, no repeats)
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == 1.5
+
+
 @pytest.mark.parametrize("extra", [[], ["--optimizer", "in_pass"], ["--optimizer", "fused"]], ids=["fwd+bwd", "in-pass adam", "fused adam"])
 def test_share_proxy_runs_one_ranks_share_with_every_collective(extra):
     """bench.py --share K: rank R's share of a K-rank strong-scaling run in ONE process (a one-member process group, the halo
@@ -90,7 +128,8 @@ def test_share_proxy_runs_one_ranks_share_with_every_collective(extra):
 def test_whole_c4_path_releases_the_originals_and_keeps_a_cpu_sample():
     """bench.py --config c4 --whole (all of configs[4] on one GPU, here shrunk): the flows are packed, the originals released — the CPU leg's
     sample copied first — and the line says so; the loss equals the run that keeps the originals."""
-    small = ["--frames", "9", "--height", "24", "--width", "32", "--points", "60", "--steps", "2", "--warmup", "1", "--cpu-frames", "4", "--cpu-iters", "1"]
+    small = ["--frames", "9", "--height", "24", "--width", "32", "--points", "60", "--steps", "2", "--warmup", "1", "--cpu-frames", "4", "--cpu-iters", "1",
+             "--full"]
     launcher = str(ROOT / "tests" / "tools" / "bench_dryrun.py")
     lines = []
     for extra in (["--whole"], []):

@@ -1,6 +1,6 @@
 import os, sys as _s; _s.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sys, runpy, collections
-sys.argv = ["bench.py", "--cpu-frames", "0", "--steps", "5", "--warmup", "3"]
+sys.argv = ["bench.py", "--full", "--cpu-frames", "0", "--steps", "5", "--warmup", "3"]
 import bench
 orig = bench.count_launches
 def counted(step, device):

@@ -13,12 +13,12 @@ for w in $what; do
     info) { free -g; nproc; lscpu | grep -i "model name"; rocm-smi --showmeminfo vram 2>/dev/null | head -8; } > $out/info.txt 2>&1 ;;
     tests) ( time python -m pytest tests -m gpu -q -rf --durations=8 ) > $out/pytest.log 2>&1; tail -30 $out/pytest.log ;;
     fasttests) ( time FLOWMAP_SKIP_FULL_SIZE=1 python -m pytest tests -m gpu -q -rf --durations=8 ) > $out/pytest.log 2>&1; tail -30 $out/pytest.log ;;
-    bench) python bench.py > $out/bench_c1.json 2> $out/bench_c1.err; cat $out/bench_c1.json ;;
-    dense) python bench.py --points 0 --cpu-frames 0 > $out/bench_dense.json 2> $out/bench_dense.err; cat $out/bench_dense.json ;;
-    track) python bench.py --tracking --cpu-frames 0 > $out/bench_c2.json 2> $out/bench_c2.err; cat $out/bench_c2.json ;;
+    bench) python bench.py --full > $out/bench_c1.json 2> $out/bench_c1.err; cat $out/bench_c1.json ;;
+    dense) python bench.py --full --points 0 --cpu-frames 0 > $out/bench_dense.json 2> $out/bench_dense.err; cat $out/bench_dense.json ;;
+    track) python bench.py --full --tracking --cpu-frames 0 > $out/bench_c2.json 2> $out/bench_c2.err; cat $out/bench_c2.json ;;
     run-*)  # run-<name>:<bench args with + for spaces>   -> one bench line
       name=${w#run-}; args=${name#*:}; name=${name%%:*}; args=${args//+/ }
-      python bench.py --cpu-frames 0 $args > $out/bench_$name.json 2> $out/bench_$name.err; cat $out/bench_$name.json; tail -3 $out/bench_$name.err ;;
+      python bench.py --full --cpu-frames 0 $args > $out/bench_$name.json 2> $out/bench_$name.err; cat $out/bench_$name.json; tail -3 $out/bench_$name.err ;;
     prof-*)  # prof-<name>:<bench args with + for spaces>, e.g. prof-dense:--points+0   -> rocprofv3 kernel stats
       name=${w#prof-}; args=${name#*:}; name=${name%%:*}; args=${args//+/ }
       (cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats -d $REPO/$out/prof_$name -o stats -- python $REPO/bench.py --steps ${PROF_STEPS:-20} --warmup ${PROF_WARMUP:-5} --cpu-frames 0 --sustained-steps 0 --ate off $args > /dev/null 2> $REPO/$out/prof_$name.err)

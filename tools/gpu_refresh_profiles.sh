@@ -19,8 +19,8 @@ stats() {  # stats <name> <bench args...>: rocprofv3 kernel trace of a short ben
 for part in $parts; do
 case $part in
 bench)
-  python bench.py > "$OUT/${R}_bench_c1.json" 2> "$OUT/bench_c1.err"   # (with the CPU baseline on the whole workload: ~70 s of host time)
-  python bench.py --config c2 > "$OUT/${R}_bench_c2_tracking.json" 2> "$OUT/bench_c2.err" ;;
+  python bench.py --full > "$OUT/${R}_bench_c1.json" 2> "$OUT/bench_c1.err"   # (with the CPU baseline on the whole workload: ~70 s of host time)
+  python bench.py --full --config c2 > "$OUT/${R}_bench_c2_tracking.json" 2> "$OUT/bench_c2.err" ;;
 variants)
   { for a in "--config c3" "--config c4" "--inputs iid" "--intrinsics softmin" "--optimizer fused" "--optimizer in_pass" "--optimizer torch" \
              "--config c2 --optimizer fused" "--config c2 --optimizer in_pass" "--intrinsics softmin --optimizer in_pass" "--points 0" \
@@ -28,7 +28,7 @@ variants)
              "--height 180 --width 240" "--height 180 --width 240 --optimizer fused" "--height 180 --width 240 --optimizer fused --graph" \
              "--height 180 --width 240 --intrinsics softmin" "--height 180 --width 240 --tracking --optimizer fused" \
              "--height 180 --width 240 --tracking --optimizer fused --graph"; do
-      python bench.py --cpu-frames 0 $a 2>> "$OUT/variants.err"; done; } > "$OUT/${R}_bench_variants.jsonl"
+      python bench.py --full --cpu-frames 0 $a 2>> "$OUT/variants.err"; done; } > "$OUT/${R}_bench_variants.jsonl"
   ;;
 proxy)
   bash tools/scaling_proxy.sh "$OUT/${R}_strong_scaling_proxy.jsonl" > "$OUT/${R}_strong_scaling_proxy_table.txt" 2>&1; cat "$OUT/${R}_strong_scaling_proxy_table.txt" ;;

@@ -10,7 +10,7 @@ for k in 1 2 4 8; do
   for mode in "--graph off" "--graph compute" "--graph whole" "--graph off --halo early" "--graph compute --halo early" "--graph whole --halo early" "--graph off --halo ghost" "--graph compute --halo ghost" "--graph whole --halo ghost"; do
     share=""; [ "$k" -gt 1 ] && share="--share $k"
     [ "$k" -eq 1 ] && [ "$mode" != "--graph off" ] && [ "$mode" != "--graph whole" ] && continue   # (one GPU: no collectives, no halo)
-    timeout 300 python bench.py --cpu-frames 0 --steps 200 --warmup 20 $share $mode "$@" >> "$out" 2>> "${out%.jsonl}.err" || echo "{\"failed\": \"--share $k $mode\"}" >> "$out"
+    timeout 300 python bench.py --full --cpu-frames 0 --steps 200 --warmup 20 $share $mode "$@" >> "$out" 2>> "${out%.jsonl}.err" || echo "{\"failed\": \"--share $k $mode\"}" >> "$out"
   done
 done
 python - "$out" <<'PY'
