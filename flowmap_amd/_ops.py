@@ -407,6 +407,8 @@ class ProcrustesFit:
         without the chain — the caller holds the relative poses and chains them if and when something asks (LazyExtrinsics)."""
         from_depth = surfaces is None
         rep = int(batch_repeat)
+        if indices is not None and indices.numel() < 3:  # (model/extrinsics_procrustes.py: check_num_points)
+            raise ValueError(f"flowmap_amd: num_points = {indices.numel()}: the Procrustes fit needs at least 3 points (fewer do not determine a rotation)")
         kinv = sink = wsink = arena = None
         sparse = (None, None, None, None, None, None)
         dense = (None, None)

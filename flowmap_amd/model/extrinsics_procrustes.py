@@ -22,6 +22,18 @@ class ExtrinsicsProcrustesCfg:
     randomize_points: bool
 
 
+MIN_POINTS = 3
+
+
+def check_num_points(num_points: Optional[int]) -> None:
+    """A rigid transformation is determined by three non-collinear correspondences.  With fewer, the centred cloud has rank
+    <= 1: the rotation about it is free (the reference returns whatever its SVD picks in the null space) and the gradient of
+    the fit carries 1/(sigma_2 + sigma_3) = 1/0.  Refused here, by name, before anything is launched."""
+    if num_points is not None and num_points < MIN_POINTS:
+        raise ValueError(f"flowmap_amd: num_points = {num_points}: the Procrustes fit needs at least {MIN_POINTS} points "
+                         "(fewer do not determine a rotation)")
+
+
 _index_cache: dict = {}
 
 
@@ -48,6 +60,7 @@ class ExtrinsicsProcrustes(nn.Module):
 
     def __init__(self, cfg: ExtrinsicsProcrustesCfg, num_frames: Optional[int] = None) -> None:
         super().__init__()
+        check_num_points(cfg.num_points)
         self.cfg = cfg
         self.num_frames = num_frames
 
@@ -59,6 +72,7 @@ class ExtrinsicsProcrustes(nn.Module):
                 twin = self.__dict__["_fm_host_twin"] = ref_cls(self.cfg, self.num_frames)
             return twin.forward(batch, flows, backbone_output, surfaces)
         _, _, h, w, _ = surfaces.shape
+        check_num_points(self.cfg.num_points)  # (the configuration may have changed since construction)
         indices = procrustes_indices(h, w, self.cfg.num_points, self.cfg.randomize_points, surfaces.device)
         # Align the depth maps using a Procrustes fit.
         # (the chain may come back unevaluated — LazyExtrinsics — while gradients are recorded and nothing has read it so far: a flow-only

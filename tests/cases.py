@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import assert_close, assert_close_or_reference_gap, load_golden, maxerr, t
+from conftest import assert_close, assert_close_or_reference_gap, load_golden, maxerr, relerr, t
 from flowmap_amd import Tracks
 from flowmap_amd.loss.mapping import get_mapping
 from flowmap_amd.model import procrustes as fp
@@ -188,7 +188,8 @@ def case_flow_loss_batched(dev, lazy):
     assert_close(loss, ref, TOL, what="loss")
     assert_close(ext, o.extrinsics, TOL, what="extrinsics")
     assert_close(d.grad, d64.grad, TOL, what="g_depth")
-    assert_close(wt.grad, w64.grad, 3 * TOL, what="g_weights")
+    print(f"\n[flow_loss_batched lazy={lazy}] g_weights {relerr(wt.grad, w64.grad):.2e}", flush=True)
+    assert_close(wt.grad, w64.grad, TOL, what="g_weights")
     # dL/dK on i.i.d. inputs is a sum that cancels to ~1e-3 of its terms: held to the fp64 truth at 1e-4, or to twice the gap the
     # reference's own fp32 evaluation (the oracle in fp32) has on the same inputs — measured here
     d32, w32, k32 = (x.detach().clone().requires_grad_(True) for x in (depth, weights, k))

@@ -7,6 +7,10 @@
 // analytic gradients can be checked against the oracle in the GPU-less build
 // container before GPU minutes are spent.  Launch geometry, coalescing, wave
 // reductions and atomics are what it does NOT cover — the `-m gpu` tests do.
+// One exception: the Procrustes moments are added up in the kernels' shape (a few
+// correspondences per lane in fp32, a 64-lane butterfly in fp32, fp64 above — SimWave
+// below), because the depth of that fp32 sum decides how accurate the fitted pose is
+// and with it the noise of dL/dweights: the CPU and GPU gates then mean the same thing.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -506,9 +510,47 @@ static SimDensePixel sim_dense_pixel(const CorrSrc& src, int row, int col) {
   return o;
 }
 
-int fm_procrustes_stats(const float* depth, const float* kinv, const float* surfaces, const float* bwd_flow,
-                        const float* weights, float sens, const int64_t* indices, long points, int batch, int repeat, int frames,
-                        int height, int width, double* stats, void*) {
+// How the kernels add the moments up, which is what decides the accuracy of the fitted pose: a thread adds ITS OWN few
+// correspondences in fp32 (one to four of a sampled set, eight pixels of a dense tile), the 64 lanes of a wave are added by a
+// butterfly in fp32 (fm_device.h: wave_sum_lane63 — lanes 1, 2, 4, 8 apart, then the rows of 16), and everything above a wave is
+// fp64.  The double used to add 256 correspondences one after the other in fp32 before going to fp64: sixteen times the depth of
+// the kernels' fp32 tree, poses 5-10x further from the fp64 fit than the GPU's (2-3e-7 against 2-6e-8) — and because the flow
+// loss is nearly stationary in the pose the fit returns, that pose error came back as a 3-15x noisier dL/dweights on the CPU
+// than on the GPU ("Numerics of the sampled fit").  SimWave is one wave: lane accumulators, then the butterfly.
+struct SimWave {
+  float lane[64][kMomentCount];
+  void clear() { std::memset(lane, 0, sizeof(lane)); }
+  void flush(double* st) {  // butterfly: both partners end with the same sum (fp32 addition commutes), lane 63 holds the wave's total
+    for (int stride = 1; stride < 64; stride <<= 1)
+      for (int l = 0; l < 64; ++l)
+        if (!(l & stride))
+          for (int k = 0; k < kMomentCount; ++k) lane[l][k] = lane[l | stride][k] = lane[l][k] + lane[l | stride][k];
+    for (int k = 0; k < kMomentCount; ++k) st[k] += (double)lane[63][k];
+  }
+};
+
+// The sampled (or surface-sourced) moments of one pair in the order of procrustes_fit_pair_kernel (`one_block`: 1024 threads,
+// thread t takes correspondences t, t + 1024, ...) or of procrustes_moments_kernel (blocks of 256 threads, `iters` each).
+static void sim_sparse_moments(const CorrSrc& src, const Mat3& ke, const Mat3& kl, const int64_t* indices, long points, const float* shift,
+                               bool one_block, double* st) {
+  const long iters = one_block ? (points + 1023) / 1024 : (points <= 65536 ? 1 : 8);
+  const long threads = one_block ? 1024 : 256, per_block = threads * iters;
+  SimWave wave;
+  for (long base = 0; base < points; base += per_block)
+    for (long w0 = 0; w0 < threads && base + w0 < points; w0 += 64) {
+      wave.clear();
+      for (int l = 0; l < 64; ++l)
+        for (long it = 0; it < iters; ++it) {
+          const long j = base + it * threads + w0 + l;
+          if (j < points) moments_add(corr_load(src, ke, kl, indices ? (int)indices[j] : (int)j), shift, wave.lane[l]);
+        }
+      wave.flush(st);
+    }
+}
+
+static int sim_procrustes_stats(const float* depth, const float* kinv, const float* surfaces, const float* bwd_flow,
+                                const float* weights, float sens, const int64_t* indices, long points, int batch, int repeat, int frames,
+                                int height, int width, double* stats, bool one_block) {
   const int pairs = batch * (frames - 1);
   std::memset(stats, 0, sizeof(double) * (size_t)pairs * kStatStride);
   const bool dense = dense_mode(depth, surfaces, indices, points, repeat, height, width);
@@ -524,13 +566,14 @@ int fm_procrustes_stats(const float* depth, const float* kinv, const float* surf
     if (dense) {  // pixel-space sums, intrinsics applied once per pair (as the tiled kernels)
       float gs[3];
       dense_shift(src.depth_l, height, width, gs);
-      for (long j0 = 0; j0 < points; j0 += 256) {
-        float acc[kMomentCount] = {};
-        for (long j = j0; j < points && j < j0 + 256; ++j) {
+      SimWave wave;  // eight pixels per lane, as a thread of procrustes_moments_dense_kernel has (its tile mapping is not mirrored)
+      for (long j0 = 0; j0 < points; j0 += 512) {
+        wave.clear();
+        for (long j = j0; j < points && j < j0 + 512; ++j) {
           const SimDensePixel px = sim_dense_pixel(src, (int)(j / width), (int)(j % width));
-          dense_moments_add(px.g, px.h, px.w, gs, acc);
+          dense_moments_add(px.g, px.h, px.w, gs, wave.lane[(j - j0) / 8]);
         }
-        for (int k = 0; k < kMomentCount; ++k) st[k] += acc[k];
+        wave.flush(st);
       }
       dense_moments_finish(st, gs, kinv + ((size_t)b * frames + i) * 9, kinv + ((size_t)b * frames + i + 1) * 9);
       continue;
@@ -538,15 +581,16 @@ int fm_procrustes_stats(const float* depth, const float* kinv, const float* surf
     float shift[3];
     const long mid = points / 2;
     later_point(src, kl, indices ? (int)indices[mid] : (int)mid, shift);
-    for (long j0 = 0; j0 < points; j0 += 256) {  // fp32 partial sums per 256 points, fp64 across (as the kernel)
-      float acc[kMomentCount] = {};
-      for (long j = j0; j < points && j < j0 + 256; ++j)
-        moments_add(corr_load(src, ke, kl, indices ? (int)indices[j] : (int)j), shift, acc);
-      for (int k = 0; k < kMomentCount; ++k) st[k] += acc[k];
-    }
+    sim_sparse_moments(src, ke, kl, indices, points, shift, one_block, st);
     moments_finish(st, shift);
   }
   return 0;
+}
+
+int fm_procrustes_stats(const float* depth, const float* kinv, const float* surfaces, const float* bwd_flow,
+                        const float* weights, float sens, const int64_t* indices, long points, int batch, int repeat, int frames,
+                        int height, int width, double* stats, void*) {
+  return sim_procrustes_stats(depth, kinv, surfaces, bwd_flow, weights, sens, indices, points, batch, repeat, frames, height, width, stats, false);
 }
 
 int fm_procrustes_dense_tiles(int height, int width, int* tiles) {
@@ -720,9 +764,9 @@ int fm_procrustes_fit_chain(const float* depth, const float* kinv, const float* 
         }
       }
   }
-  if (fm_procrustes_fit(depth, kinv, surfaces, bwd_flow, weights, sens, indices, points, batch, 1, frames, height, width, stats.data(), t_bwd,
-                        t_fwd, aux, stream) != 0)
-    return 2;
+  // (up to 4096 points the device's chained fit is procrustes_fit_pair_kernel, one block per pair)
+  sim_procrustes_stats(depth, kinv, surfaces, bwd_flow, weights, sens, indices, points, batch, 1, frames, height, width, stats.data(), points <= 4096);
+  if (fm_pose_solve(stats.data(), pairs, t_bwd, t_fwd, aux, stream) != 0) return 2;
   if (corr_out) {  // the record of every correspondence, as the device kernel leaves it (corr_record_core)
     if (points > 4096 || !tap_records) return 1;
     for (int b = 0; b < batch; ++b)
