@@ -224,6 +224,7 @@ FM_HD int tap_row(const Taps& t, int k) { return t.y0 + (k >> 1); }
 // consistency_mask_at: FlowPredictor.compute_consistency_mask (:60-80) at ONE source pixel:
 //   target colour = grid_sample(target, (xy + flow)·2 − 1, bilinear, padding "zeros",
 //   align_corners=False);  δ = max_c |source_c − target_c|;  mask = (1 − δ)⁸.
+// A flow that is NaN or ±inf gives a NaN mask, as the reference's grid_sample + max do.
 // src / tgt address one frame stored (3, H, W).
 // ---------------------------------------------------------------------------------
 FM_HD float consistency_mask_at(const float* src, const float* tgt, int h, int w, int row, int col, float flow_x, float flow_y) {
@@ -237,7 +238,7 @@ FM_HD float consistency_mask_at(const float* src, const float* tgt, int h, int w
   // the float -> int conversions saturate, so far-away samples simply fail the range tests
   const float cx = fminf(fmaxf(fx, -2.f), (float)w + 1.f), cy = fminf(fmaxf(fy, -2.f), (float)h + 1.f);
   const int x0 = (int)cx, y0 = (int)cy;
-  const bool ok = ix == ix && iy == iy;  // NaN coordinates sample nothing
+  const bool ok = ix == ix && iy == iy;  // (a NaN coordinate reads no tap; its NaN weights make `sampled` NaN all the same)
   const bool xin0 = ok && x0 >= 0 && x0 < w, xin1 = ok && x0 + 1 >= 0 && x0 + 1 < w;
   const bool yin0 = ok && y0 >= 0 && y0 < h, yin1 = ok && y0 + 1 >= 0 && y0 + 1 < h;
   const size_t plane = (size_t)h * w;
@@ -249,7 +250,10 @@ FM_HD float consistency_mask_at(const float* src, const float* tgt, int h, int w
     const float sw = (xin0 && yin1) ? t[(size_t)(y0 + 1) * w + x0] : 0.f;
     const float se = (xin1 && yin1) ? t[(size_t)(y0 + 1) * w + x0 + 1] : 0.f;
     const float sampled = nw * (wn * ww) + ne * (wn * we) + sw * (ws * ww) + se * (ws * we);
-    delta = fmaxf(delta, fabsf(src[c * plane + (size_t)row * w + col] - sampled));
+    // torch.max over the channels: a NaN (a NaN or ±inf flow: inf − inf in the weights) propagates into the mask, where fmaxf would
+    // drop it and leave δ = 0, i.e. full confidence.  For finite operands this is fmaxf.
+    const float d = fabsf(src[c * plane + (size_t)row * w + col] - sampled);
+    if (d > delta || d != d) delta = d;
   }
   const float b = 1.f - delta, b2 = b * b, b4 = b2 * b2;
   return b4 * b4;

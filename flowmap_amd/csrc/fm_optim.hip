@@ -9,6 +9,8 @@
 // (m = v = 0 -> step 0/(0+eps) = 0), so their three stores are skipped — bit-identical, and
 // it is the common case for the correspondence weights: only the P Procrustes sample points
 // of each pair (1000 of 921 600 at C1) ever receive a gradient (extrinsics_procrustes.py:45-52).
+// The premise needs eps > 0: with eps = 0 the update of such an element is 0/0 = NaN (torch's answer), which the vector body
+// would skip and the scalar tail would not.  The entry points therefore refuse eps <= 0 (as rounded to fp32).
 #include "fm_device.h"
 #include "fm_math.h"
 
@@ -121,7 +123,7 @@ extern "C" {
 int fm_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long count, long step, double lr, double beta1,
                  double beta2, double eps, double weight_decay, void* stream) {
   FM_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && count >= 0 && step >= 1);
-  FM_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0);
+  FM_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && (float)eps > 0.f);  // eps: see the header of this file
   if (count == 0) return FM_OK;
   const AdamCoef c = adam_coefficients((double)step, lr, beta1, beta2, eps, weight_decay);
   auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
@@ -137,7 +139,7 @@ int fm_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
 int fm_adam_step_capturable(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long count, const float* step,
                             double lr, double beta1, double beta2, double eps, double weight_decay, void* stream) {
   FM_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && step && count >= 0);
-  FM_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0);
+  FM_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && (float)eps > 0.f);  // eps: see the header of this file
   if (count == 0) return FM_OK;
   auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   const int vec_ok = aligned(param) && aligned(grad) && aligned(exp_avg) && aligned(exp_avg_sq);
@@ -152,7 +154,7 @@ int fm_adam_step_capturable(float* param, const float* grad, float* exp_avg, flo
 int fm_adam_step_elements(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* elements, long count, long step,
                           double lr, double beta1, double beta2, double eps, double weight_decay, void* stream) {
   FM_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && count >= 0 && step >= 1 && (elements || count == 0));
-  FM_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0);
+  FM_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && (float)eps > 0.f);  // eps: see the header of this file
   if (count == 0) return FM_OK;
   const AdamCoef c = adam_coefficients((double)step, lr, beta1, beta2, eps, weight_decay);
   hipLaunchKernelGGL(adam_elements_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,

@@ -17,6 +17,15 @@ import torch
 from ._lib import check_device, torch_ops
 
 
+def _check_eps(eps) -> None:
+    """torch.optim.Adam accepts eps = 0 and then turns an element with g = m = v = 0 into 0 / 0 = NaN.  Here such elements are
+    never visited at all — the idle quads of the kernel, the element-list update of a sparse gradient, the in-pass depth update
+    — because 0 / (0 + eps) = 0 leaves them where they are, which holds for eps > 0 only."""
+    if not float(torch.tensor(float(eps), dtype=torch.float32)) > 0.0:  # (the kernels hold eps in fp32)
+        raise ValueError(f"flowmap_amd.FusedAdam: the zero-gradient shortcuts need eps > 0 in fp32 (got {eps}); torch.optim.Adam's eps = 0 "
+                         "divides 0 by 0 for every element that has not seen a gradient yet")
+
+
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params: Iterable, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, amsgrad: bool = False, *, maximize: bool = False, capturable: bool = False) -> None:
@@ -25,6 +34,7 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError(f"Invalid learning rate: {lr}")
         if not 0.0 <= eps:
             raise ValueError(f"Invalid epsilon value: {eps}")
+        _check_eps(eps)
         if not 0.0 <= betas[0] < 1.0:
             raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
         if not 0.0 <= betas[1] < 1.0:
@@ -131,6 +141,7 @@ class FusedAdam(torch.optim.Optimizer):
         if (group is None or group["weight_decay"] != 0 or group.get("capturable") or not param.is_contiguous() or param.dtype != torch.float32
                 or depth.data_ptr() != param.data_ptr() or depth.numel() != param.numel()):
             return None
+        _check_eps(group["eps"])
         if depth.dim() != 4 or depth.shape[-1] % 4 != 0 or depth.data_ptr() % 16 != 0:
             return None  # the 16-byte vector path of the fused pass does not apply (fm_flow_loss_fused_adam would refuse)
         if param in self._in_pass:
@@ -183,6 +194,8 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        for group in self.param_groups:  # (a group's eps can have been changed since construction; nothing has moved yet)
+            _check_eps(group["eps"])
         for group in self.param_groups:
             beta1, beta2 = group["betas"]
             for p in group["params"]:

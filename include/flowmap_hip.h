@@ -618,7 +618,8 @@ int fm_world_points(const float* depth, const float* kinv, const float* ext, con
 /* ---- flow post-processing ---------------------------------------
  * FlowPredictor.compute_consistency_mask (flowmap/flow/flow_predictor.py:60-80):
  * videos (B,F,3,H,W), flow (B,F-1,H,W,2) in normalised image units -> mask (B,F-1,H,W) =
- * (1 - max_c |frame_i - bilinear(frame_{i+1}, xy + flow)|)^8, zeros padding. */
+ * (1 - max_c |frame_i - bilinear(frame_{i+1}, xy + flow)|)^8, zeros padding; NaN where the flow is NaN or ±inf, as the
+ * reference's grid_sample + max give.  batch·(frames-1) <= 65535 (else: the argument error, nothing is launched). */
 int fm_consistency_mask(const float* videos, const float* flow, int batch, int frames, int height, int width, float* mask,
                         void* stream);
 
@@ -651,7 +652,10 @@ int fm_fill_zero(float* x, long count, int blocks, void* stream);
  * (flowmap/model/model_wrapper_overfit.py:104-105), one tensor per call, in place:
  *   g += weight_decay·p; m = m + (1-β1)(g-m); v = β2·v + (1-β2)g²;
  *   p -= lr/(1-β1^step) · m / (sqrt(v)/sqrt(1-β2^step) + eps)
- * `step` is the 1-based step number AFTER the increment.  No amsgrad / maximize. */
+ * `step` is the 1-based step number AFTER the increment.  No amsgrad / maximize.
+ * eps must be positive as an fp32 (else: the argument error).  Elements with g = m = v = 0 and no weight decay are fixed
+ * points of the update only because 0/(0+eps) = 0; the 16-byte body skips their stores, and torch's eps = 0 (0/0 = NaN
+ * for them) would give one tensor both answers.  The same holds for _capturable and _elements below. */
 int fm_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long count, long step, double lr, double beta1,
                  double beta2, double eps, double weight_decay, void* stream);
 

@@ -12,6 +12,7 @@
 // below), because the depth of that fp32 sum decides how accurate the fitted pose is
 // and with it the noise of dL/dweights: the CPU and GPU gates then mean the same thing.
 #include <algorithm>
+#include <cstdint>
 #include <cstring>
 #include <vector>
 
@@ -382,6 +383,7 @@ int fm_world_points(const float* depth, const float* kinv, const float* ext, con
 }
 
 int fm_consistency_mask(const float* videos, const float* flow, int batch, int frames, int height, int width, float* mask, void*) {
+  if (batch < 1 || frames < 2 || (long)batch * (frames - 1) > 65535) return 1;  // the library's launch limit (grid.y)
   const size_t n = (size_t)height * width;
   for (int bp = 0; bp < batch * (frames - 1); ++bp) {
     const int b = bp / (frames - 1), pair = bp % (frames - 1);
@@ -395,6 +397,7 @@ int fm_consistency_mask(const float* videos, const float* flow, int batch, int f
 
 int fm_flow_postprocess(const float* videos, const float* flow, int batch, int frames, int height, int width, int out_height,
                         int out_width, int reverse, float* out_flow, float* out_mask, void*) {
+  if (batch < 1 || frames < 2 || (long)batch * (frames - 1) > 65535) return 1;  // the library's launch limit (grid.y)
   const size_t n = (size_t)height * width, on = (size_t)out_height * out_width;
   for (int bp = 0; bp < batch * (frames - 1); ++bp) {
     const int b = bp / (frames - 1), pair = bp % (frames - 1);
@@ -427,19 +430,21 @@ int fm_resize_crop(const float* in, long planes, int h, int w, int rh, int rw, i
 
 int fm_adam_step_elements(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* elements, long count, long step,
                           double lr, double beta1, double beta2, double eps, double weight_decay, void*) {
-  if (!param || !grad || !exp_avg || !exp_avg_sq || step < 1 || (count > 0 && !elements)) return 1;
+  if (!param || !grad || !exp_avg || !exp_avg_sq || step < 1 || (count > 0 && !elements) || !((float)eps > 0.f)) return 1;
   const AdamCoef c = adam_coefficients((double)step, lr, beta1, beta2, eps, weight_decay);
   for (long i = 0; i < count; ++i) adam_update(c, param[elements[i]], grad[elements[i]], exp_avg[elements[i]], exp_avg_sq[elements[i]]);
   return 0;
 }
 
-int fm_fill_zero(float* x, long count, int, void*) {
+int fm_fill_zero(float* x, long count, int blocks, void*) {
+  if (!x || count < 0 || blocks < 1 || (reinterpret_cast<uintptr_t>(x) & 15) != 0) return 1;  // the library's argument checks
   for (long i = 0; i < count; ++i) x[i] = 0.f;
   return 0;
 }
 
 int fm_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long count, long step, double lr, double beta1,
                  double beta2, double eps, double weight_decay, void*) {
+  if (!param || !grad || !exp_avg || !exp_avg_sq || count < 0 || step < 1 || !((float)eps > 0.f)) return 1;
   const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
   AdamCoef c{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)(lr / bc1), (float)std::sqrt(bc2), (float)eps,
              (float)weight_decay};
@@ -449,6 +454,8 @@ int fm_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
 
 int fm_adam_step_capturable(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long count, const float* step, double lr,
                             double beta1, double beta2, double eps, double weight_decay, void* stream) {
+  if (!step || !((float)eps > 0.f)) return 1;
+  if (count == 0) return 0;
   return fm_adam_step(param, grad, exp_avg, exp_avg_sq, count, (long)step[0], lr, beta1, beta2, eps, weight_decay, stream);
 }
 
