@@ -21,6 +21,7 @@ STAT_STRIDE = 16
 AUX_STRIDE = 40
 PAIR_GRAD_STRIDE = 20
 DENSE_CONST_STRIDE = 40  # FM_DENSE_CONST_STRIDE
+FLOW_BITMASK_CHUNK_BYTES = 4160  # FM_FLOW_BITMASK_CHUNK_BYTES (include/flowmap_hip.h; tests/test_hostsim_flow_bitmask.py checks they agree)
 TRACK_TILE = 6  # FM_TRACK_TILE (include/flowmap_hip.h; tests/test_abi.py checks they agree)
 
 

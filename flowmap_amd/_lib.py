@@ -110,6 +110,10 @@ SIGNATURES = {
     "fm_depth_gather": [P, P, P, P, P, L, P, P, P, I, I, L, P, P],
     "fm_depth_gather_kgrad": [P, P, P, P, P, L, P, I, I, P, P, I, P, I, P],
     "fm_procrustes_bwd_planned": [P, P, F, L, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, I, P],
+    "fm_flow_masks_binary": [P, P, I, I, L, P, P, P],
+    "fm_flow_pack_inputs_bitmask": [P, P, P, P, I, I, I, I, P, P],
+    "fm_flow_pack_inputs_bitmask_views": [P, P, P, P, I, I, I, I, P, P, P],
+    "fm_flow_loss_fused_bitmask": [P] * 7 + [I, I, I, I, I, F, F, F, P, P, I, P, P, P, P, P, L, D, D, D, D, P],
 }
 
 _lib: Optional[ctypes.CDLL] = None

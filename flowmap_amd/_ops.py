@@ -30,7 +30,7 @@ from torch import Tensor
 from ._lib import call, check_device, ptr, stream_for, torch_ops
 from .config import options
 
-from ._base import (AUX_STRIDE, DENSE_CONST_STRIDE, FLOW_ACC_STRIDE, MAPPING_KINDS, PAIR_GRAD_STRIDE, STAT_STRIDE, TRACK_TILE, FmLayout,  # noqa: F401
+from ._base import (AUX_STRIDE, DENSE_CONST_STRIDE, FLOW_ACC_STRIDE, FLOW_BITMASK_CHUNK_BYTES, MAPPING_KINDS, PAIR_GRAD_STRIDE, STAT_STRIDE, TRACK_TILE, FmLayout,  # noqa: F401
                     _derived, _f32c, _guard, _layout_array, _unit_flags, check_unit_flags, frame_window_layout, register_unit_flag)
 
 
@@ -230,7 +230,7 @@ def _dense_flow_is_rough(bwd_flow: Tensor, h: int, w: int) -> bool:
     return _derived(bwd_flow, "_fm_dense_rough", (bwd_flow._version, h, w), build)
 
 # which backward path the facades selected (tests)
-counters = {"procrustes_planned": 0, "procrustes_dense_planned": 0, "flow_packs": 0, "procrustes_plans_built": 0, "track_tap_samples": 0,
+counters = {"procrustes_planned": 0, "procrustes_dense_planned": 0, "flow_packs": 0, "flow_packs_bitmask": 0, "procrustes_plans_built": 0, "track_tap_samples": 0,
             "flow_tap_passes": 0, "flow_tap_absorbs": 0}
 
 
@@ -505,7 +505,10 @@ def flow_valid_norm(mask_fwd: Tensor, mask_bwd: Tensor, weight: float, reducer=N
 
 
 def packed_flow_inputs(flow_fwd: Tensor, flow_bwd: Tensor, mask_fwd: Tensor, mask_bwd: Tensor, eager: bool = False) -> Optional[Tensor]:
-    """Flows + masks in the layout of fm_flow_pack_inputs, or None when it does not apply
+    """Flows + masks in the layout of fm_flow_pack_inputs (float32, (…, 6, 64, 4)) — or, when every mask value is +0.0f or 1.0f, of
+    fm_flow_pack_inputs_bitmask (uint8, (…, FLOW_BITMASK_CHUNK_BYTES): the masks as one bit per pixel and direction; the classification is
+    one more read pass and one flag read-back at pack time, never during a stream capture; ``options.packed_bitmask = False`` forces the
+    fp32 format) — or None when it does not apply
     (width not a multiple of 4, unexpected shapes / dtypes) — or not YET: the re-layout is a full read + write pass over
     the flows and masks (+3.3 GB resident at C1), worth it only for inputs that come back.  In an overfit loop they are
     constants (flow_predictor.py:82-102 runs once per video) and the SECOND step that brings the same four tensors packs
@@ -527,7 +530,7 @@ def packed_flow_inputs(flow_fwd: Tensor, flow_bwd: Tensor, mask_fwd: Tensor, mas
     lay, any_view = _layout_array(*srcs)
     if lay is None or any(lay[i].frame_stride % 4 or lay[i].batch_stride % 4 for i in range(4)):
         return None
-    key = tuple((id(t), t._version, t.data_ptr()) for t in srcs) + (tuple(mask_fwd.shape),)
+    key = tuple((id(t), t._version, t.data_ptr()) for t in srcs) + (tuple(mask_fwd.shape), bool(options.packed_bitmask))
     if not (eager or options.pack_on_first_sight):
         slot = flow_fwd.__dict__.get("_fm_packed")
         if (slot is None or slot[0] != key) and flow_fwd.__dict__.get("_fm_packed_seen") != key:
@@ -537,6 +540,27 @@ def packed_flow_inputs(flow_fwd: Tensor, flow_bwd: Tensor, mask_fwd: Tensor, mas
     def build():
         b, pairs, h, w = mask_fwd.shape
         chunks = (h * w // 4 + 63) // 64
+        # the format is decided here, once per cached entry: bits when both masks hold nothing but +0.0f / 1.0f.  (The decision needs a host
+        # read of one flag: a pack that happens inside a stream capture keeps the fp32 format.)
+        bitmask = bool(options.packed_bitmask) and not (mask_fwd.is_cuda and torch.cuda.is_current_stream_capturing())
+        if bitmask:
+            flag = torch.ones((1,), dtype=torch.int32, device=mask_fwd.device)
+            with _guard(mask_fwd.device):
+                call("fm_flow_masks_binary", ptr(mask_fwd), ptr(mask_bwd), b, pairs, h * w, ptr(flag), ctypes.addressof(lay) + 2 * ctypes.sizeof(lay[0]),
+                     stream_for(mask_fwd))
+            bitmask = int(flag.item()) == 0
+        if bitmask:
+            packed = torch.empty((b * (pairs + 1), chunks, FLOW_BITMASK_CHUNK_BYTES), dtype=torch.uint8, device=mask_fwd.device)
+            with _guard(mask_fwd.device):
+                if any_view:
+                    call("fm_flow_pack_inputs_bitmask_views", ptr(flow_fwd), ptr(flow_bwd), ptr(mask_fwd), ptr(mask_bwd), b, pairs + 1, h, w, ptr(packed),
+                         ctypes.addressof(lay), stream_for(mask_fwd))
+                else:
+                    call("fm_flow_pack_inputs_bitmask", ptr(flow_fwd), ptr(flow_bwd), ptr(mask_fwd), ptr(mask_bwd), b, pairs + 1, h, w, ptr(packed),
+                         stream_for(mask_fwd))
+            counters["flow_packs"] += 1
+            counters["flow_packs_bitmask"] += 1
+            return (srcs[1:], packed)
         packed = torch.empty((b * (pairs + 1), chunks, 6, 64, 4), dtype=torch.float32, device=mask_fwd.device)
         with _guard(mask_fwd.device):
             if any_view:

@@ -36,6 +36,10 @@ class Options:
     packed_inputs: bool = True
     # tests: pack the first time a set of flows is seen (a one-step test then runs the packed kernel instance)
     pack_on_first_sight: bool = False
+    # Masks whose every value is +0.0f or 1.0f (thresholded consistency / occlusion masks) are packed as one bit per pixel and direction
+    # (fm_flow_pack_inputs_bitmask: 16.25 instead of 24 bytes per pixel and frame, dL/ddepth bit-identical); anything else keeps the fp32
+    # packed format.  False forces the fp32 format for every input (old/new comparisons, tests).
+    packed_bitmask: bool = True
     # sample the tracking loss's tap depths from the image the flow pass leaves (while the parameter's version counter has not moved)
     tap_image: bool = True
     # The tap exchange pays where the depth images are far larger than the last-level cache (256 MB of Infinity Cache on an MI355X): at

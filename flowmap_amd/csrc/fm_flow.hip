@@ -36,7 +36,8 @@ struct FlowParams {
   const float* flow_bwd;  // (B,F-1,H,W,2)
   const float* mask_fwd;  // (B,F-1,H,W)
   const float* mask_bwd;  // (B,F-1,H,W)
-  const float* packed;    // (B·F, chunks, 6, 64, 4) re-laid-out flows + masks (fm_flow_pack_inputs) or null
+  const float* packed;    // (B·F, chunks, 6, 64, 4) re-laid-out flows + masks (fm_flow_pack_inputs), the bit-mask form of it
+                          // ((B·F, chunks, kBitChunkBytes) bytes, fm_flow_pack_inputs_bitmask) or null
   const float* scale;     // device scalar multiplied into every per-residual gradient
   float* grad_depth;      // (B,F,H,W) or null
   double* acc;            // (B*F, 2, kFlowAccStride)
@@ -130,6 +131,33 @@ __device__ __forceinline__ void load_quad_packed(QuadIn& q, const float* depth, 
     q.bc = ld4(packed, base + 4 * kPackLanes);
     q.bm = ld4(packed, base + 5 * kPackLanes);
   }
+}
+
+// Bit-mask layout (fm_flow_pack_inputs_bitmask), for masks whose every value is +0.0f or 1.0f: a chunk is the four flow vectors of its
+// 64 quads (4 KB, [vector 0..3][lane]: forward flow x2, backward flow x2) followed by ONE byte per lane — bits 0-3 the forward mask of
+// the quad's four pixels, bits 4-7 the backward mask — 16.25 instead of 24 bytes per pixel.  The mask is expanded back to 0.0f / 1.0f
+// here and everything after the loads is the arithmetic of the fp32 layout, bit for bit.
+constexpr int kBitVecs = 4;
+constexpr int kBitChunkBytes = FM_FLOW_BITMASK_CHUNK_BYTES;
+static_assert(kBitChunkBytes >= kBitVecs * kPackLanes * 16 + kPackLanes && kBitChunkBytes % 16 == 0, "a chunk holds 4 KB of flows + 64 mask bytes");
+enum : int { kFmtNone = 0, kFmtF32 = 1, kFmtBits = 2 };  // the PACKED parameter of flow_fused_kernel
+
+__device__ __forceinline__ void load_quad_bits(QuadIn& q, const float* depth, const uint8_t* packed, int item, bool has_fwd, bool has_bwd) {
+  q.z = ld4(depth, item);
+  const uint8_t* chunk = packed + (size_t)(item / kPackLanes) * kBitChunkBytes;
+  const float* flows = reinterpret_cast<const float*>(chunk);
+  const int lane = item % kPackLanes;
+  if (has_fwd) {
+    q.fa = ld4(flows, lane);
+    q.fc = ld4(flows, lane + kPackLanes);
+  }
+  if (has_bwd) {
+    q.ba = ld4(flows, lane + 2 * kPackLanes);
+    q.bc = ld4(flows, lane + 3 * kPackLanes);
+  }
+  const unsigned bits = FM_LOAD(chunk + kBitVecs * kPackLanes * 16 + lane);  // (an absent direction's nibble is zero)
+  q.fm.x = bits & 1u ? 1.f : 0.f, q.fm.y = bits & 2u ? 1.f : 0.f, q.fm.z = bits & 4u ? 1.f : 0.f, q.fm.w = bits & 8u ? 1.f : 0.f;
+  q.bm.x = bits & 16u ? 1.f : 0.f, q.bm.y = bits & 32u ? 1.f : 0.f, q.bm.z = bits & 64u ? 1.f : 0.f, q.bm.w = bits & 128u ? 1.f : 0.f;
 }
 
 // ---------------------------------------------------------------------------------
@@ -232,8 +260,33 @@ __device__ __forceinline__ void flow_term_pair(const DirPair& d, v2f arow, v2f b
 #define FM_FLOW_WAVES 3
 #endif
 
-template <int VEC, int KIND, bool GRAD, bool PACKED, bool ADAM = false, bool TAPS = false>
-__global__ void __launch_bounds__(256, FM_FLOW_WAVES) flow_fused_kernel(FlowParams p) {
+// The bit-mask instances move a quarter fewer bytes and wait less for HBM: there the balance tips towards issue and latency hiding, and
+// the SCALAR form of the two terms (110 VGPRs) beats the packed pair — C1, kernel alone, 5 / 4 / 3 quads per thread: 0.615 / 0.625 /
+// 0.645 ms at 4 waves per SIMD (0.614 / 0.619 / 0.619 at 3: no difference) against 0.697 / 0.726 / 0.789 for the packed pair at 3 (and
+// 1.22-1.28 ms for the packed pair squeezed into 4 waves: it spills); profiles/r07_bitmask_kernel_variants.txt.  The fp32 instances keep
+// the packed pair at FM_FLOW_WAVES.  The bit-mask instances with the tap exchange run the scalar form at FM_FLOW_WAVES (their LDS
+// bookkeeping does not fit 128 VGPRs: 16-76 bytes of scratch per lane at 4 waves; C2 kernel 0.70 -> 0.65 ms against the packed pair).
+// Both forms perform the operations of flow_term_fast in the same order per component, and the scalar form is kept from contracting the
+// four statements the packed pair leaves uncontracted (fm_math.h: UNFUSED_SUMS): dL/ddepth AND the 13 sums are the same bits.
+#ifndef FM_FLOW_WAVES_BITS
+#define FM_FLOW_WAVES_BITS 4
+#endif
+#ifdef FM_FLOW_SCALAR_TERMS
+constexpr bool kScalarTermsEverywhere = true;
+constexpr bool kUnfusedSums = false;  // (the whole-library A/B build: the scalar form as the compiler contracts it, as before)
+#else
+constexpr bool kScalarTermsEverywhere = false;
+constexpr bool kUnfusedSums = true;  // the scalar form of the bit-mask instances rounds its sums where the packed pair does (fm_math.h)
+#endif
+#ifdef FM_FLOW_BITS_PAIR_TERMS  // (A/B: the bit-mask instances on the packed pair of terms, like the fp32 ones)
+constexpr bool kScalarTermsBits = false;
+#else
+constexpr bool kScalarTermsBits = true;
+#endif
+
+template <int VEC, int KIND, bool GRAD, int PACKED, bool ADAM = false, bool TAPS = false>
+__global__ void __launch_bounds__(256, (PACKED == kFmtBits && !TAPS) ? FM_FLOW_WAVES_BITS : FM_FLOW_WAVES) flow_fused_kernel(FlowParams p) {
+  constexpr bool SCALAR = kScalarTermsEverywhere || (PACKED == kFmtBits && kScalarTermsBits);
   static_assert(!ADAM || (VEC == 4 && GRAD), "the in-pass Adam update runs on the 16-byte gradient path");
   static_assert(!TAPS || (VEC == 4 && GRAD), "the tap exchange runs on the 16-byte gradient path");
   extern __shared__ double lds[];  // reduction scratch (fp64), then the [width] u-table, then (TAPS) the two tap images of the block's pixels
@@ -293,17 +346,16 @@ __global__ void __launch_bounds__(256, FM_FLOW_WAVES) flow_fused_kernel(FlowPara
   const float* fb = p.flow_bwd + (size_t)b * p.bs[2] + (size_t)(f - 1) * p.fs[2];  // pair f−1 (never dereferenced for f = 0)
   const float* mb = p.mask_bwd + (size_t)b * p.bs[4] + (size_t)(f - 1) * p.fs[4];
   const size_t chunks = ((size_t)items + kPackLanes - 1) / kPackLanes;
-  const float* packed = PACKED ? p.packed + (size_t)bf * chunks * (kPackVecs * kPackLanes * 4) : nullptr;
+  const float* packed = PACKED == kFmtF32 ? p.packed + (size_t)bf * chunks * (kPackVecs * kPackLanes * 4) : nullptr;
+  const uint8_t* packed_bits = PACKED == kFmtBits ? reinterpret_cast<const uint8_t*>(p.packed) + (size_t)bf * chunks * kBitChunkBytes : nullptr;
   float* gd = GRAD && p.grad_depth ? p.grad_depth + (size_t)bf * n : nullptr;
 
   v2f acc[kFlowAcc];  // x: towards the next frame, y: towards the previous one
 #pragma unroll
   for (int i = 0; i < kFlowAcc; ++i) acc[i] = pk1(0.f);
-#ifdef FM_FLOW_SCALAR_TERMS
-  float sacc_f[kFlowAcc], sacc_b[kFlowAcc];
+  float sacc_f[kFlowAcc], sacc_b[kFlowAcc];  // (SCALAR form only)
 #pragma unroll
   for (int i = 0; i < kFlowAcc; ++i) sacc_f[i] = sacc_b[i] = 0.f;
-#endif
 
   const int base = blockIdx.x * (blockDim.x * p.iters);
 
@@ -316,7 +368,7 @@ __global__ void __launch_bounds__(256, FM_FLOW_WAVES) flow_fused_kernel(FlowPara
     const float v = pixel_center(row, p.height);
     const float v_ay = v * p.ay;
     // a1·v + a2 (and b, c alike) is constant along the image row the quad lies in
-#ifdef FM_FLOW_SCALAR_TERMS  // (A/B: the two directions one after the other in plain fp32, behind wave-uniform run-time tests)
+    if constexpr (SCALAR) {  // the two directions one after the other in plain fp32, behind wave-uniform run-time tests
     const float rf0 = fmaf(df.a1, v, df.a2), rf1 = fmaf(df.b1, v, df.b2), rf2 = fmaf(df.c1, v, df.c2);
     const float rb0 = fmaf(db.a1, v, db.a2), rb1 = fmaf(db.b1, v, db.b2), rb2 = fmaf(db.c1, v, db.c2);
 #pragma unroll
@@ -325,11 +377,11 @@ __global__ void __launch_bounds__(256, FM_FLOW_WAVES) flow_fused_kernel(FlowPara
       const float zu = z[e] * u, zv = z[e] * v, u_ax = u * p.ax;
       gz[e] = 0.f;
       if (has_fwd)
-        flow_term_fast<KIND, GRAD>(df, rf0, rf1, rf2, z[e], u, zu, zv, u_ax, v_ay, fxf[e], fyf[e], mmf[e], scale, p.delta, inv_delta, p.ax, p.ay, sacc_f, gz[e]);
+        flow_term_fast<KIND, GRAD, kUnfusedSums>(df, rf0, rf1, rf2, z[e], u, zu, zv, u_ax, v_ay, fxf[e], fyf[e], mmf[e], scale, p.delta, inv_delta, p.ax, p.ay, sacc_f, gz[e]);
       if (has_bwd)
-        flow_term_fast<KIND, GRAD>(db, rb0, rb1, rb2, z[e], u, zu, zv, u_ax, v_ay, fxb[e], fyb[e], mmb[e], scale, p.delta, inv_delta, p.ax, p.ay, sacc_b, gz[e]);
+        flow_term_fast<KIND, GRAD, kUnfusedSums>(db, rb0, rb1, rb2, z[e], u, zu, zv, u_ax, v_ay, fxb[e], fyb[e], mmb[e], scale, p.delta, inv_delta, p.ax, p.ay, sacc_b, gz[e]);
     }
-#else
+    } else {
     const v2f v2 = pk1(v);
     const v2f arow = pk_fma(dp.a1, v2, dp.a2), brow = pk_fma(dp.b1, v2, dp.b2), crow = pk_fma(dp.c1, v2, dp.c2);
 #pragma unroll
@@ -340,7 +392,7 @@ __global__ void __launch_bounds__(256, FM_FLOW_WAVES) flow_fused_kernel(FlowPara
       flow_term_pair<KIND, GRAD>(dp, arow, brow, crow, z[e], u, zu, zv, u_ax, v_ay, pk(fxf[e], fxb[e]), pk(fyf[e], fyb[e]), pk(mmf[e], mmb[e]),
                                  scale, p.delta, inv_delta, p.ax, p.ay, acc, gz[e]);
     }
-#endif
+    }
     const int local_quad = item - block_quad0;
     if (TAPS) {
       if (p.tap_grad) {  // (wave-uniform) the tracking loss's share of dL/ddepth at this quad's pixels: zero off the taps
@@ -421,7 +473,8 @@ __global__ void __launch_bounds__(256, FM_FLOW_WAVES) flow_fused_kernel(FlowPara
     }
     const int item0 = base + (int)threadIdx.x;
     if (item0 < items) {
-      if constexpr (PACKED) load_quad_packed(q_first, depth, packed, item0, has_fwd, has_bwd);
+      if constexpr (PACKED == kFmtBits) load_quad_bits(q_first, depth, packed_bits, item0, has_fwd, has_bwd);
+      else if constexpr (PACKED == kFmtF32) load_quad_packed(q_first, depth, packed, item0, has_fwd, has_bwd);
       else load_quad(q_first, depth, ff, mf, fb, mb, item0, has_fwd, has_bwd);
     }
     my_tap_pixel -= 4 * block_quad0;
@@ -439,7 +492,8 @@ __global__ void __launch_bounds__(256, FM_FLOW_WAVES) flow_fused_kernel(FlowPara
     if (VEC == 4) {
       QuadIn q = {};
       if (TAPS && it == 0) q = q_first;
-      else if constexpr (PACKED) load_quad_packed(q, depth, packed, item, has_fwd, has_bwd);
+      else if constexpr (PACKED == kFmtBits) load_quad_bits(q, depth, packed_bits, item, has_fwd, has_bwd);
+      else if constexpr (PACKED == kFmtF32) load_quad_packed(q, depth, packed, item, has_fwd, has_bwd);
       else load_quad(q, depth, ff, mf, fb, mb, item, has_fwd, has_bwd);
       compute_quad(q, item);
       continue;
@@ -494,10 +548,10 @@ __global__ void __launch_bounds__(256, FM_FLOW_WAVES) flow_fused_kernel(FlowPara
   float acc_f[kFlowAcc], acc_b[kFlowAcc];
 #pragma unroll
   for (int i = 0; i < kFlowAcc; ++i) acc_f[i] = acc[i].x, acc_b[i] = acc[i].y;
-#ifdef FM_FLOW_SCALAR_TERMS
+  if constexpr (SCALAR) {
 #pragma unroll
-  for (int i = 0; i < kFlowAcc; ++i) acc_f[i] = sacc_f[i], acc_b[i] = sacc_b[i];
-#endif
+    for (int i = 0; i < kFlowAcc; ++i) acc_f[i] = sacc_f[i], acc_b[i] = sacc_b[i];
+  }
   if (has_fwd) block_accumulate<kFlowAcc>(acc_f, red, dst);
   if (has_bwd) block_accumulate<kFlowAcc>(acc_b, red, dst + kFlowAccStride);
 }
@@ -598,6 +652,53 @@ struct PackLayouts {
   long fs[4], bs[4];  // flow_fwd, flow_bwd, mask_fwd, mask_bwd
 };
 
+// The bit-mask form (load_quad_bits): per chunk the four flow vectors, then one byte per lane — bit e = forward mask of pixel e of the
+// quad is non-zero, bit 4 + e = backward mask; the bytes between a chunk's 64 mask bytes and the next chunk (none at the default
+// stride) are zero.  The caller has established that every mask value is +0.0f or 1.0f (fm_flow_masks_binary).
+__global__ void __launch_bounds__(256) pack_inputs_bitmask_kernel(const float* flow_fwd, const float* flow_bwd, const float* mask_fwd,
+                                                                  const float* mask_bwd, int frames, int n, uint8_t* packed, PackLayouts lay) {
+  const int quads = n / 4;
+  const int chunks = (quads + kPackLanes - 1) / kPackLanes;
+  const int bf = blockIdx.y, f = bf % frames, b = bf / frames;
+  const bool has_fwd = f < frames - 1, has_bwd = f > 0;
+  const v4f zero = {0.f, 0.f, 0.f, 0.f};
+  uint8_t* out = packed + (size_t)bf * chunks * kBitChunkBytes;
+  const v4f* ff = reinterpret_cast<const v4f*>(flow_fwd + (size_t)b * lay.bs[0] + (size_t)f * lay.fs[0]);
+  const v4f* fb = reinterpret_cast<const v4f*>(flow_bwd + (size_t)b * lay.bs[1] + (size_t)(f - 1) * lay.fs[1]);
+  const v4f* mf = reinterpret_cast<const v4f*>(mask_fwd + (size_t)b * lay.bs[2] + (size_t)f * lay.fs[2]);
+  const v4f* mb = reinterpret_cast<const v4f*>(mask_bwd + (size_t)b * lay.bs[3] + (size_t)(f - 1) * lay.fs[3]);
+  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < chunks * kPackLanes; q += gridDim.x * blockDim.x) {
+    const bool live = q < quads;
+    const int lane = q % kPackLanes;
+    uint8_t* chunk = out + (size_t)(q / kPackLanes) * kBitChunkBytes;
+    v4f* o = reinterpret_cast<v4f*>(chunk) + lane;
+    o[0 * kPackLanes] = live && has_fwd ? ff[2 * q] : zero;
+    o[1 * kPackLanes] = live && has_fwd ? ff[2 * q + 1] : zero;
+    o[2 * kPackLanes] = live && has_bwd ? fb[2 * q] : zero;
+    o[3 * kPackLanes] = live && has_bwd ? fb[2 * q + 1] : zero;
+    const v4f a = live && has_fwd ? mf[q] : zero, c = live && has_bwd ? mb[q] : zero;
+    const unsigned bits = (a.x != 0.f ? 1u : 0u) | (a.y != 0.f ? 2u : 0u) | (a.z != 0.f ? 4u : 0u) | (a.w != 0.f ? 8u : 0u) |
+                          (c.x != 0.f ? 16u : 0u) | (c.y != 0.f ? 32u : 0u) | (c.z != 0.f ? 64u : 0u) | (c.w != 0.f ? 128u : 0u);
+    chunk[kBitVecs * kPackLanes * 16 + lane] = (uint8_t)bits;
+    for (int pad = kBitVecs * kPackLanes * 16 + kPackLanes + lane; pad < kBitChunkBytes; pad += kPackLanes) chunk[pad] = 0;
+  }
+}
+
+// *not_binary = 1 when an element of either mask stack has another bit pattern than +0.0f or 1.0f (−0.0f, NaN, 0.5, 1 + 1 ulp ...):
+// such masks keep the fp32 packed format.  Same launch geometry as sum2_kernel.
+__global__ void __launch_bounds__(256) masks_binary_kernel(const float* a, const float* b, long n, int frames_per_batch, long fs_a, long bs_a,
+                                                           long fs_b, long bs_b, int* not_binary) {
+  const int fr = blockIdx.y % frames_per_batch, be = blockIdx.y / frames_per_batch;
+  const float* pa = a + (size_t)be * bs_a + (size_t)fr * fs_a;
+  const float* pb = b + (size_t)be * bs_b + (size_t)fr * fs_b;
+  bool other = false;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const unsigned ua = __float_as_uint(pa[i]), ub = __float_as_uint(pb[i]);
+    other = other || (ua != 0u && ua != 0x3f800000u) || (ub != 0u && ub != 0x3f800000u);
+  }
+  if (other) *not_binary = 1;
+}
+
 __global__ void __launch_bounds__(256) pack_inputs_kernel(const float* flow_fwd, const float* flow_bwd, const float* mask_fwd,
                                                           const float* mask_bwd, int frames, int n, float* packed, PackLayouts lay) {
   const int quads = n / 4;
@@ -651,8 +752,10 @@ static int flow_loss_launch(const float* depth, const float* k, const float* kin
                             const float* flow_fwd, const float* flow_bwd, const float* mask_fwd, const float* mask_bwd,
                             const float* packed, const float* scale, int batch, int frames, int height, int width,
                             int mapping_kind, float delta, float aspect_x, float aspect_y, float* grad_depth, double* acc,
-                            int items_per_thread, const FlowAdam* adam, const fm_layout* layouts, void* stream, const fm_flow_taps* taps = nullptr) {
+                            int items_per_thread, const FlowAdam* adam, const fm_layout* layouts, void* stream, const fm_flow_taps* taps = nullptr,
+                            bool bitmask = false) {
   FM_CHECK_ARG(depth && k && kinv && acc);
+  FM_CHECK_ARG(!bitmask || packed);  // (`packed` then points at the bytes of fm_flow_pack_inputs_bitmask)
   FM_CHECK_ARG(!(layouts && adam));  // the in-pass update rewrites the depth PARAMETER: dense by construction
   FM_CHECK_ARG(!taps || (!layouts && taps->chunk_base && taps->pixel && scale && grad_depth && width % 4 == 0 && (taps->grad == nullptr || taps->scale != nullptr)));
   FM_CHECK_ARG(packed || (flow_fwd && flow_bwd && mask_fwd && mask_bwd));
@@ -714,6 +817,9 @@ static int flow_loss_launch(const float* depth, const float* k, const float* kin
     p.iters = 4;
     // (with the tap exchange a workgroup pays a fixed set-up — its taps' LDS images, two barriers —: five quads per thread first.  C2,
     // 230 400 quads per frame: 0.78 ms against 0.80 with four, 0.83 with three, 0.95 with six; gpurun_out r04r / r04s)
+    // (the bit-mask instances keep these orders: five quads per thread measured 1.6 % faster than four on the kernel alone — 0.615 against
+    // 0.625 ms at C1, three 0.645 — but another split of a frame into workgroups regroups the fp32 partial sums behind the 13 totals, and the
+    // step's gradients then differ from the fp32 format's in their last bits instead of being equal; profiles/r07_bitmask_kernel_variants.txt)
     const int order_plain[3] = {4, 3, 5}, order_taps[3] = {5, 4, 3};
     for (int cand : (taps ? order_taps : order_plain))
       if (items % ((long)threads * cand) == 0) {
@@ -746,16 +852,17 @@ static int flow_loss_launch(const float* depth, const float* k, const float* kin
   } while (0)
 #define FM_FLOW_VEC(V)                 \
   do {                                 \
-    if (use_packed) FM_FLOW_KIND(V, true); \
-    else FM_FLOW_KIND(V, false);       \
+    if (bitmask) FM_FLOW_KIND(V, kFmtBits); \
+    else if (use_packed) FM_FLOW_KIND(V, kFmtF32); \
+    else FM_FLOW_KIND(V, kFmtNone);    \
   } while (0)
   FM_CHECK_ARG(!adam || (vec == 4 && grad && grad_depth));
   FM_CHECK_ARG(!taps || vec == 4);
   if (vec == 4) FM_FLOW_VEC(4);
 #ifdef FM_FLOW_FORCE_VEC2
-  else if (vec == 2) FM_FLOW_KIND(2, false);
+  else if (vec == 2) FM_FLOW_KIND(2, kFmtNone);
 #endif
-  else FM_FLOW_KIND(1, false);
+  else FM_FLOW_KIND(1, kFmtNone);
 #undef FM_FLOW_VEC
 #undef FM_FLOW_KIND
 #undef FM_FLOW_LAUNCH
@@ -814,6 +921,30 @@ int fm_flow_loss_fused_taps(float* depth, const float* k, const float* kinv, con
                           mapping_kind, delta, aspect_x, aspect_y, grad_depth, acc, items_per_thread, &adam, nullptr, stream, taps);
 }
 
+int fm_flow_loss_fused_bitmask(float* depth, const float* k, const float* kinv, const float* t_fwd, const float* t_bwd, const uint8_t* packed,
+                               const float* scale, int batch, int frames, int height, int width, int mapping_kind, float delta, float aspect_x,
+                               float aspect_y, float* grad_depth, double* acc, int items_per_thread, const fm_layout* depth_layout,
+                               const fm_flow_taps* taps, float* exp_avg, float* exp_avg_sq, const uint8_t* touched, long step, double lr, double beta1,
+                               double beta2, double eps, void* stream) {
+  FM_CHECK_ARG(packed != nullptr);
+  const float* pk = reinterpret_cast<const float*>(packed);
+  fm_layout lay[5] = {};  // (only the depth stack is read beside the packed bytes)
+  if (depth_layout) lay[0] = depth_layout[0];
+  const fm_layout* layouts = depth_layout && (lay[0].frame_stride != 0 || lay[0].batch_stride != 0) ? lay : nullptr;
+  if (exp_avg == nullptr) {
+    FM_CHECK_ARG(exp_avg_sq == nullptr && touched == nullptr);
+    return flow_loss_launch(depth, k, kinv, t_fwd, t_bwd, nullptr, nullptr, nullptr, nullptr, pk, scale, batch, frames, height, width, mapping_kind,
+                            delta, aspect_x, aspect_y, grad_depth, acc, items_per_thread, nullptr, layouts, stream, taps, true);
+  }
+  FM_CHECK_ARG(exp_avg_sq && touched && scale && grad_depth && step >= 1 && width % 4 == 0);
+  FM_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0);
+  auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  FM_CHECK_ARG(aligned(exp_avg) && aligned(exp_avg_sq));
+  const FlowAdam adam{exp_avg, exp_avg_sq, touched, adam_coefficients((double)step, lr, beta1, beta2, eps, 0.0)};
+  return flow_loss_launch(depth, k, kinv, t_fwd, t_bwd, nullptr, nullptr, nullptr, nullptr, pk, scale, batch, frames, height, width, mapping_kind,
+                          delta, aspect_x, aspect_y, grad_depth, acc, items_per_thread, &adam, layouts, stream, taps, true);
+}
+
 int fm_flow_loss_finalize(double* acc, const float* k, const float* kinv, const float* t_fwd, const float* t_bwd,
                           const float* norm, int batch, int frames, float aspect_x, float aspect_y, float* loss, float* g_t_fwd,
                           float* g_t_bwd, float* g_k, void* stream) {
@@ -860,7 +991,8 @@ int fm_flow_valid_norm_views(const float* mask_fwd, const float* mask_bwd, int b
 }
 
 static int pack_launch(const float* flow_fwd, const float* flow_bwd, const float* mask_fwd, const float* mask_bwd, int batch,
-                       int frames, int height, int width, float* packed, const fm_layout* layouts, void* stream) {
+                       int frames, int height, int width, float* packed, const fm_layout* layouts, void* stream, uint8_t* packed_bits = nullptr) {
+  if (packed_bits) packed = reinterpret_cast<float*>(packed_bits);
   FM_CHECK_ARG(flow_fwd && flow_bwd && mask_fwd && mask_bwd && packed);
   FM_CHECK_ARG(batch >= 1 && frames >= 2 && height >= 1 && width >= 1 && width % 4 == 0 && (long)batch * frames <= 65535);
   auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
@@ -876,8 +1008,12 @@ static int pack_launch(const float* flow_fwd, const float* flow_bwd, const float
   }
   int bx = (quads + 255) / 256;
   if (bx > 2048) bx = 2048;
-  hipLaunchKernelGGL(pack_inputs_kernel, dim3((unsigned)bx, (unsigned)(batch * frames)), dim3(256), 0, (hipStream_t)stream, flow_fwd,
-                     flow_bwd, mask_fwd, mask_bwd, frames, n, packed, lay);
+  if (packed_bits)
+    hipLaunchKernelGGL(pack_inputs_bitmask_kernel, dim3((unsigned)bx, (unsigned)(batch * frames)), dim3(256), 0, (hipStream_t)stream, flow_fwd,
+                       flow_bwd, mask_fwd, mask_bwd, frames, n, packed_bits, lay);
+  else
+    hipLaunchKernelGGL(pack_inputs_kernel, dim3((unsigned)bx, (unsigned)(batch * frames)), dim3(256), 0, (hipStream_t)stream, flow_fwd,
+                       flow_bwd, mask_fwd, mask_bwd, frames, n, packed, lay);
   FM_LAUNCH_STATUS();
 }
 
@@ -889,6 +1025,38 @@ int fm_flow_pack_inputs(const float* flow_fwd, const float* flow_bwd, const floa
 int fm_flow_pack_inputs_views(const float* flow_fwd, const float* flow_bwd, const float* mask_fwd, const float* mask_bwd, int batch,
                               int frames, int height, int width, float* packed, const fm_layout* layouts, void* stream) {
   return pack_launch(flow_fwd, flow_bwd, mask_fwd, mask_bwd, batch, frames, height, width, packed, layouts, stream);
+}
+
+int fm_flow_pack_inputs_bitmask(const float* flow_fwd, const float* flow_bwd, const float* mask_fwd, const float* mask_bwd, int batch,
+                                int frames, int height, int width, uint8_t* packed, void* stream) {
+  FM_CHECK_ARG(packed != nullptr);
+  return pack_launch(flow_fwd, flow_bwd, mask_fwd, mask_bwd, batch, frames, height, width, nullptr, nullptr, stream, packed);
+}
+
+int fm_flow_pack_inputs_bitmask_views(const float* flow_fwd, const float* flow_bwd, const float* mask_fwd, const float* mask_bwd, int batch,
+                                      int frames, int height, int width, uint8_t* packed, const fm_layout* layouts, void* stream) {
+  FM_CHECK_ARG(packed != nullptr);
+  return pack_launch(flow_fwd, flow_bwd, mask_fwd, mask_bwd, batch, frames, height, width, nullptr, layouts, stream, packed);
+}
+
+int fm_flow_masks_binary(const float* mask_fwd, const float* mask_bwd, int batch, int pairs, long pixels, int* not_binary,
+                         const fm_layout* layouts, void* stream) {
+  FM_CHECK_ARG(mask_fwd && mask_bwd && not_binary && batch >= 1 && pairs >= 1 && pixels >= 1 && (long)batch * pairs <= 65535);
+  hipStream_t st = (hipStream_t)stream;
+  long fs[2], bs[2];
+  for (int i = 0; i < 2; ++i) {
+    const bool given = layouts && (layouts[i].frame_stride != 0 || layouts[i].batch_stride != 0);
+    fs[i] = given ? layouts[i].frame_stride : pixels;
+    bs[i] = given ? layouts[i].batch_stride : pixels * pairs;
+    FM_CHECK_ARG(fs[i] >= pixels);
+  }
+  if (hipMemsetAsync(not_binary, 0, sizeof(int), st) != hipSuccess) return FM_ERR_LAUNCH;
+  long blocks = (pixels + 256 * 16 - 1) / (256 * 16);
+  const long cap = 4096 / ((long)batch * pairs) + 1;
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(masks_binary_kernel, dim3((unsigned)blocks, (unsigned)(batch * pairs)), dim3(256), 0, st, mask_fwd, mask_bwd, pixels, pairs, fs[0],
+                     bs[0], fs[1], bs[1], not_binary);
+  FM_LAUNCH_STATUS();
 }
 
 int fm_abi_version(void) { return FM_ABI_VERSION; }

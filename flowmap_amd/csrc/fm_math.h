@@ -379,7 +379,11 @@ FM_HD void make_dir(const Pose& pose, const Mat3& kinv, const Mat3& kd, float ax
 }
 
 // arow / brow / crow = a1·v + a2 etc. (constant along an image row); u_ax, v_ay = aspect·(u, v).
-template <int KIND, bool GRAD>
+// UNFUSED_SUMS (device, the bit-mask instances of flow_fused_kernel): the compiler contracts `n - 0.5·delta` and `acc += q·w` into fused
+// multiply-adds in this plain-fp32 form but leaves them as v_pk_mul / v_pk_add in the packed pair of directions (flow_term_pair): with
+// contraction off for those four statements the two forms round at the same places and the 13 sums come out as the same bits (measured on
+// one-workgroup frames, all three mappings).  The host double is built with -ffp-contract=off: both settings are the same code there.
+template <int KIND, bool GRAD, bool UNFUSED_SUMS = false>
 FM_HD void flow_term_fast(const DirConst& d, float arow, float brow, float crow, float z, float u, float zu, float zv, float u_ax,
                           float v_ay, float flow_x, float flow_y, float m, float scale, float delta, float inv_delta, float ax,
                           float ay, float (&acc)[kFlowAcc], float& gz) {
@@ -410,7 +414,14 @@ FM_HD void flow_term_fast(const DirConst& d, float arow, float brow, float crow,
       coef = inv_n;
     } else {
       const bool quad = n < delta;
-      rho = quad ? 0.5f * ss * inv_delta : n - 0.5f * delta;
+      if (UNFUSED_SUMS) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+        rho = quad ? 0.5f * ss * inv_delta : n - 0.5f * delta;
+      } else {
+        rho = quad ? 0.5f * ss * inv_delta : n - 0.5f * delta;
+      }
       coef = quad ? inv_delta : inv_n;
     }
   }
@@ -419,9 +430,18 @@ FM_HD void flow_term_fast(const DirConst& d, float arow, float brow, float crow,
     const float gc = (scale * m) * coef;
     const float wu = gc * rx, wv = gc * ry;  // dL/d(kd·p)
     const float o0 = q * wu, o1 = q * wv, o2 = q * fmaf(wu, pu, wv * pv);
-    acc[1] += o0;
-    acc[2] += o1;
-    acc[3] += o2;
+    if (UNFUSED_SUMS) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+      acc[1] += o0;
+      acc[2] += o1;
+      acc[3] += o2;
+    } else {
+      acc[1] += o0;
+      acc[2] += o1;
+      acc[3] += o2;
+    }
     acc[4] = fmaf(o0, zu, acc[4]);
     acc[5] = fmaf(o0, zv, acc[5]);
     acc[6] = fmaf(o0, z, acc[6]);
@@ -1215,3 +1235,9 @@ FM_HD void dense_bwd_s(const DenseBwd& c, const float h[3], const float t[3], co
 }
 
 }  // namespace fm
+
+// A host build of the C ABI from these headers (no hipcc: the serial double of the library that the CPU test-suite runs the package on)
+// takes the bit-mask entry points of the fused flow loss from here, written over the fp32-format entry points it defines itself.
+#if !defined(__HIPCC__)
+#include "fm_flow_bitmask_host.h"
+#endif

@@ -49,7 +49,8 @@ using OptTensor = std::optional<Tensor>;
   X(fm_relative_pose_bwd) X(fm_procrustes_fit) X(fm_procrustes_fit_chain) X(fm_depth_gather_kgrad) X(fm_pose_solve_bwd) X(fm_pose_solve_bwd_kinv) X(fm_procrustes_scatter) X(fm_procrustes_scatter_dense) X(fm_procrustes_bwd_planned) X(fm_flow_loss_fused_views) X(fm_procrustes_fit_chain_views) X(fm_procrustes_fit_views) X(fm_procrustes_scatter_views)                \
   X(fm_depth_gather) X(fm_extrinsics_inverse) X(fm_track_loss_fused_fwd) X(fm_track_loss_bwd) X(fm_adam_step)                 \
   X(fm_adam_step_capturable) X(fm_softmin_score_fwd) X(fm_softmin_score_bwd) X(fm_softmin_blend_fwd) X(fm_softmin_blend_bwd)         \
-  X(fm_random_subset) X(fm_random_subset_stateful) X(fm_abi_version) X(fm_flow_loss_fused_taps) X(fm_track_loss_fused_fwd_taps) X(fm_tap_grad_apply)
+  X(fm_random_subset) X(fm_random_subset_stateful) X(fm_abi_version) X(fm_flow_loss_fused_taps) X(fm_track_loss_fused_fwd_taps) X(fm_tap_grad_apply) \
+  X(fm_flow_loss_fused_bitmask)
 
 struct Api {
 #define X(name) decltype(&::name) name = nullptr;
@@ -848,7 +849,18 @@ static FlowLaunch flow_launch(const Tensor& depth, const Tensor& k, const Tensor
   }
   const float *p_ff = pk ? nullptr : ptr(flow_fwd), *p_fb = pk ? nullptr : ptr(flow_bwd), *p_mf = pk ? nullptr : ptr(mask_fwd),
               *p_mb = pk ? nullptr : ptr(mask_bwd);
-  if (taps.on()) {  // the tap exchange with the tracking loss, with or without the in-pass Adam update (fm_flow_loss_fused_taps)
+  const bool bits = pk && packed.scalar_type() == at::kByte;  // the bit-mask format (fm_flow_pack_inputs_bitmask): one entry point for every variant
+  if (bits) {
+    TORCH_CHECK(!any_view || !(taps.on() || exp_avg.defined()), "flowmap_amd: the tap exchange and the in-pass Adam update read a dense depth stack");
+    const fm_flow_taps t{ptr<int32_t>(taps.chunk_base), ptr<int32_t>(taps.pixel), ptr(taps.grad), ptr(taps.scale), ptr(taps.depth_out),
+                         exp_avg.defined() ? nullptr : ptr<int32_t>(taps.stale)};
+    const bool ad = exp_avg.defined();
+    const bool with_grad = need || ad || taps.on();
+    FM_CALL(fm_flow_loss_fused_bitmask, ptr(depth), ptr(k), ptr(kinv), ptr(t_fwd), ptr(t_bwd), ptr<uint8_t>(packed), with_grad ? ptr(norm) : nullptr, (int)b,
+            (int)f, (int)h, (int)w, (int)kind, (float)delta, (float)w / scale, (float)h / scale, ptr(o.g_depth), ptr<double>(acc), (int)items,
+            any_view ? lay : nullptr, taps.on() ? &t : nullptr, ptr(exp_avg), ptr(exp_avg_sq), ptr<uint8_t>(touched), (long)adam_step, ad ? adam[0] : 0.0,
+            ad ? adam[1] : 0.0, ad ? adam[2] : 0.0, ad ? adam[3] : 0.0, scope.stream);
+  } else if (taps.on()) {  // the tap exchange with the tracking loss, with or without the in-pass Adam update (fm_flow_loss_fused_taps)
     TORCH_CHECK(!any_view, "flowmap_amd: the tap exchange reads dense image stacks (the caller hands frame windows to the plain pass)");
     const fm_flow_taps t{ptr<int32_t>(taps.chunk_base), ptr<int32_t>(taps.pixel), ptr(taps.grad), ptr(taps.scale), ptr(taps.depth_out),
                          exp_avg.defined() ? nullptr : ptr<int32_t>(taps.stale)};
@@ -919,10 +931,13 @@ struct FlowLossFused : public Function<FlowLossFused> {
     TORCH_CHECK(norm.scalar_type() == at::kFloat && norm.numel() >= 1, "flowmap_amd: the normaliser must be a float32 device tensor");
     TORCH_CHECK(!flow_fwd_in.requires_grad() && !flow_bwd_in.requires_grad(), "flowmap_amd: gradients w.r.t. optical flow are not supported (flows are constants)");
     Tensor packed = opt(packed_o);
-    if (packed.defined())
-      TORCH_CHECK(packed.scalar_type() == at::kFloat && packed.is_contiguous() && w % 4 == 0 &&
-                      packed.sizes() == at::IntArrayRef({b * f, (h * w / 4 + 63) / 64, 6, 64, 4}),
+    if (packed.defined()) {
+      // float32 (…, 6, 64, 4): fm_flow_pack_inputs; uint8 (…, FM_FLOW_BITMASK_CHUNK_BYTES): fm_flow_pack_inputs_bitmask (binary masks)
+      const bool f32_format = packed.scalar_type() == at::kFloat && packed.sizes() == at::IntArrayRef({b * f, (h * w / 4 + 63) / 64, 6, 64, 4});
+      const bool bit_format = packed.scalar_type() == at::kByte && packed.sizes() == at::IntArrayRef({b * f, (h * w / 4 + 63) / 64, FM_FLOW_BITMASK_CHUNK_BYTES});
+      TORCH_CHECK((f32_format || bit_format) && packed.is_contiguous() && w % 4 == 0 && packed.device() == depth.device(),
                   "flowmap_amd: packed flow inputs do not match the depth shape");
+    }
     const bool need = grad_enabled && (depth_in.requires_grad() || k_in.requires_grad() || t_fwd_in.requires_grad() || t_bwd_in.requires_grad());
     // In-pass Adam (FusedAdam.fuse_depth_update): depth itself is rewritten, so it must be the caller's memory, not a copy;
     // the update assumes the gradient is final as computed, i.e. that the loss reaches backward() unscaled

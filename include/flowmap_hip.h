@@ -39,8 +39,9 @@ extern "C" {
  * call; fm_scale_if_needed reports a non-unit scalar; round 4, version 4: the tap exchange entry
  * points fm_flow_loss_fused_taps / fm_track_loss_fused_fwd_taps / fm_tap_grad_apply; round 5, version 5: fm_tap_grad_apply reports a
  * non-zero correction through a device flag; fm_track_presample and the `presampled` argument of fm_track_loss_fused_fwd_taps; round 6,
- * version 6: that entry point and that argument are gone again — measured, not adopted: docs/history/patches/r05_track_presample.patch).  A binding checks fm_abi_version() == FM_ABI_VERSION when it loads the library. */
-#define FM_ABI_VERSION 6
+ * version 6: that entry point and that argument are gone again — measured, not adopted: docs/history/patches/r05_track_presample.patch; version 7: the bit-mask packed format of the fused flow
+ * loss — fm_flow_masks_binary, fm_flow_pack_inputs_bitmask(_views), fm_flow_loss_fused_bitmask; the existing entries are unchanged).  A binding checks fm_abi_version() == FM_ABI_VERSION when it loads the library. */
+#define FM_ABI_VERSION 7
 int fm_abi_version(void);
 
 #define FM_STAT_STRIDE 16      /* doubles per pair in `stats` */
@@ -667,6 +668,37 @@ int fm_adam_step_capturable(float* param, const float* grad, float* exp_avg, flo
  * fm_flow_loss_fused_adam. */
 int fm_adam_step_elements(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* elements, long count, long step,
                           double lr, double beta1, double beta2, double eps, double weight_decay, void* stream);
+
+/* ---- bit-mask packed inputs of the fused flow loss (version 7) ------------------------
+ * Masks that were thresholded (consistency / occlusion masks cut to 0 or 1) carry one bit per pixel: for such masks the
+ * packed copy stores the mask of a quad's four pixels and both directions in ONE byte instead of two float4, 16.25 instead
+ * of 24 bytes per pixel and frame; the pass then moves N·(8.25·F + 16·(F−1)) bytes instead of N·(8·F + 24·(F−1)).  The kernel
+ * rebuilds 0.0f / 1.0f from the bits and runs the arithmetic of the fp32 format unchanged: dL/ddepth is bit-identical.
+ *
+ * fm_flow_masks_binary: not_binary[0] (one int32 on the device) = 0 when EVERY element of both mask stacks
+ *   (batch, pairs, pixels) has the bit pattern of +0.0f or of 1.0f, else 1 (−0.0f, NaN, 0.5, 1.0f + 1 ulp ... all select the
+ *   fp32 format).  layouts[2] = mask_fwd, mask_bwd, or NULL (dense).  One read pass; the caller reads the flag back.
+ * fm_flow_pack_inputs_bitmask(_views): as fm_flow_pack_inputs(_views), into (B·F, ceil(H·W/256), FM_FLOW_BITMASK_CHUNK_BYTES)
+ *   bytes: per source frame and chunk of 64 quads four float4 vectors [vector][lane] — forward flow of pair f (2), backward
+ *   flow of pair f−1 (2) — then one byte per lane: bit e = forward mask of pixel e of the quad, bit 4 + e = backward mask.
+ *   Absent pairs and padding lanes are zero.  A mask element counts as set when it is non-zero.
+ * fm_flow_loss_fused_bitmask: fm_flow_loss_fused / _views / _adam / _taps reading that copy.  depth_layout: NULL or ONE
+ *   fm_layout (the depth stack; must be NULL with taps or the Adam update); taps: NULL or the tap exchange; exp_avg: NULL or
+ *   the in-pass Adam update (then exp_avg_sq, touched, step >= 1 as in fm_flow_loss_fused_adam). */
+#ifndef FM_FLOW_BITMASK_CHUNK_BYTES /* (a build flag only for A/B measurements of a padded chunk stride) */
+#define FM_FLOW_BITMASK_CHUNK_BYTES 4160 /* 4 x 64 x 16 bytes of flows + 64 mask bytes */
+#endif
+int fm_flow_masks_binary(const float* mask_fwd, const float* mask_bwd, int batch, int pairs, long pixels, int* not_binary,
+                         const fm_layout* layouts, void* stream);
+int fm_flow_pack_inputs_bitmask(const float* flow_fwd, const float* flow_bwd, const float* mask_fwd, const float* mask_bwd, int batch,
+                                int frames, int height, int width, uint8_t* packed, void* stream);
+int fm_flow_pack_inputs_bitmask_views(const float* flow_fwd, const float* flow_bwd, const float* mask_fwd, const float* mask_bwd, int batch,
+                                      int frames, int height, int width, uint8_t* packed, const fm_layout* layouts, void* stream);
+int fm_flow_loss_fused_bitmask(float* depth, const float* k, const float* kinv, const float* t_fwd, const float* t_bwd, const uint8_t* packed,
+                               const float* scale, int batch, int frames, int height, int width, int mapping_kind, float delta, float aspect_x,
+                               float aspect_y, float* grad_depth, double* acc, int items_per_thread, const fm_layout* depth_layout,
+                               const fm_flow_taps* taps, float* exp_avg, float* exp_avg_sq, const uint8_t* touched, long step, double lr, double beta1,
+                               double beta2, double eps, void* stream);
 
 #ifdef __cplusplus
 }

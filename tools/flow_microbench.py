@@ -1,5 +1,12 @@
 """A/B timing of fm_flow_loss_fused across build variants (build_variants/*.so), GRAD on/off
-and items-per-thread, interleaved in one process on identical C1-sized inputs."""
+and items-per-thread, interleaved in one process on identical C1-sized inputs.
+
+    python tools/flow_microbench.py [ITEMS,ITEMS,...] [--format fp32|bits|both]
+
+--format bits / both: the masks are thresholded to 0.0f / 1.0f and the bit-mask packed format (fm_flow_pack_inputs_bitmask,
+fm_flow_loss_fused_bitmask) is timed — `both`: next to the fp32 packed format on the same inputs.  Every library packs its own copy, so a
+variant built with another -DFM_FLOW_BITMASK_CHUNK_BYTES reads the layout it was built for."""
+import argparse
 import ctypes
 import glob
 import sys
@@ -11,6 +18,11 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from flowmap_amd import _lib  # noqa: E402
 
+ap = argparse.ArgumentParser()
+ap.add_argument("items", nargs="?", default=None, help="comma-separated items per thread (default: 2,4,6,8 on both the streamed and the packed layout)")
+ap.add_argument("--format", choices=["fp32", "bits", "both"], default="fp32")
+args = ap.parse_args()
+
 P, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 dev = "cuda:0"
 f, h, w = 150, 720, 1280
@@ -20,6 +32,8 @@ ff = 0.01 * torch.randn((1, f - 1, h, w, 2), device=dev, generator=g)
 fb = 0.01 * torch.randn((1, f - 1, h, w, 2), device=dev, generator=g)
 mf = torch.rand((1, f - 1, h, w), device=dev, generator=g)
 mb = torch.rand((1, f - 1, h, w), device=dev, generator=g)
+if args.format != "fp32":  # binary masks: what the bit-mask format is for
+    mf, mb = (mf < 0.7).float(), (mb < 0.7).float()
 fx = 0.85 * (h * w) ** 0.5
 k = torch.tensor([[fx / w, 0, 0.5], [0, fx / h, 0.5], [0, 0, 1.0]], device=dev).expand(1, f, 3, 3).contiguous()
 kinv = torch.linalg.inv(k).contiguous()
@@ -31,20 +45,38 @@ gd = torch.empty_like(depth)
 acc = torch.zeros((f * 2 * 20,), dtype=torch.float64, device=dev)  # the kernel adds into it (timing only: never finalised)
 sc = (h * w) ** 0.5
 algo = h * w * (8 * f + 24 * (f - 1))
+algo_bits = h * w * (8.25 * f + 16 * (f - 1))
+BITS_MAX_CHUNK = 4352  # room for a variant's padded chunk stride
 
 libs = {"shipped": str(_lib.LIB_PATH)}
 for p in sorted(glob.glob(str(ROOT / "build_variants" / "*.so"))):
     libs[Path(p).stem.replace("libfm_", "")] = p
-fns = {}
+fns, fns_bits, packed_bits = {}, {}, {}
 for name, path in libs.items():
-    fn = ctypes.CDLL(path).fm_flow_loss_fused
+    lib = ctypes.CDLL(path)
+    fn = lib.fm_flow_loss_fused
     fn.argtypes = _lib.SIGNATURES["fm_flow_loss_fused"]
     fn.restype = I
     fns[name] = fn
+    if args.format != "fp32":
+        fb_ = lib.fm_flow_loss_fused_bitmask
+        fb_.argtypes = _lib.SIGNATURES["fm_flow_loss_fused_bitmask"]
+        fb_.restype = I
+        fns_bits[name] = fb_
+        pack_bits = lib.fm_flow_pack_inputs_bitmask
+        pack_bits.argtypes = _lib.SIGNATURES["fm_flow_pack_inputs_bitmask"]
+        pack_bits.restype = I
+        packed_bits[name] = torch.zeros((f, (h * w // 4 + 63) // 64, BITS_MAX_CHUNK), dtype=torch.uint8, device=dev)
+        assert pack_bits(ff.data_ptr(), fb.data_ptr(), mf.data_ptr(), mb.data_ptr(), 1, f, h, w, packed_bits[name].data_ptr(),
+                         torch.cuda.current_stream().cuda_stream) == 0
 
 
-def launch(fn, grad, ipt):
+def launch(fn, grad, ipt, name=None):
     st = torch.cuda.current_stream().cuda_stream
+    if PACKED[0] == "bits":
+        return fns_bits[name](depth.data_ptr(), k.data_ptr(), kinv.data_ptr(), t.data_ptr(), t.data_ptr(), packed_bits[name].data_ptr(),
+                              norm.data_ptr() if grad else None, 1, f, h, w, 0, 0.01, w / sc, h / sc, gd.data_ptr() if grad else None, acc.data_ptr(), ipt,
+                              None, None, None, None, None, 0, 0.0, 0.0, 0.0, 0.0, st)
     return fn(depth.data_ptr(), k.data_ptr(), kinv.data_ptr(), t.data_ptr(), t.data_ptr(), ff.data_ptr(), fb.data_ptr(), mf.data_ptr(),
               mb.data_ptr(), packed.data_ptr() if PACKED[0] else None, norm.data_ptr() if grad else None, 1, f, h, w, 0, 0.01, w / sc, h / sc, gd.data_ptr() if grad else None,
               acc.data_ptr(), ipt, st)
@@ -55,9 +87,13 @@ pack.argtypes = _lib.SIGNATURES["fm_flow_pack_inputs"]
 packed = torch.empty((f, (h * w // 4 + 63) // 64, 6, 64, 4), device=dev)
 assert pack(ff.data_ptr(), fb.data_ptr(), mf.data_ptr(), mb.data_ptr(), 1, f, h, w, packed.data_ptr(), torch.cuda.current_stream().cuda_stream) == 0
 PACKED = [False]
-IPT = tuple(int(x) for x in sys.argv[1].split(",")) if len(sys.argv) > 1 else (2, 4, 6, 8)
-PKS = (True,) if len(sys.argv) > 1 else (False, True)
-configs = [(n, True, i, pk) for n in fns for i in IPT for pk in PKS] + [("shipped", False, 4, False), ("shipped", False, 4, True)]
+IPT = tuple(int(x) for x in args.items.split(",")) if args.items else (2, 4, 6, 8)
+PKS = (True,) if args.items else (False, True)
+if args.format == "bits":
+    PKS = ("bits",)
+elif args.format == "both":
+    PKS = (True, "bits")
+configs = [(n, True, i, pk) for n in fns for i in IPT for pk in PKS] + [("shipped", False, 4, pk) for pk in ((False, True) if args.format == "fp32" else PKS)]
 times = {c: [] for c in configs}
 for rnd in range(6):
     for c in configs:
@@ -65,7 +101,7 @@ for rnd in range(6):
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
         for _ in range(3):
-            assert launch(fns[name], grad, ipt) == 0
+            assert launch(fns[name], grad, ipt, name) == 0
         e.record()
         torch.cuda.synchronize()
         if rnd > 0:
@@ -73,4 +109,6 @@ for rnd in range(6):
 for c, v in times.items():
     v.sort()
     med = v[len(v) // 2]
-    print(f"{c[0]:8s} grad={int(c[1])} ipt={c[2]:2d} packed={int(c[3])}  median {med:.4f} ms  min {v[0]:.4f}  -> {algo / med / 1e6:.0f} GB/s algorithmic (grad=1 bytes)")
+    true_bytes = algo_bits if c[3] == "bits" else algo
+    print(f"{c[0]:8s} grad={int(c[1])} ipt={c[2]:2d} packed={c[3] if c[3] == 'bits' else int(c[3])}  median {med:.4f} ms  min {v[0]:.4f}  -> {algo / med / 1e6:.0f} GB/s "
+          f"fp32-mask-equivalent, {true_bytes / med / 1e6:.0f} GB/s moved (grad=1 bytes)")
