@@ -19,6 +19,7 @@ GPU tensors never reach it, and without ``install()`` there is nothing to hand o
 from . import config, flow, loss, model  # noqa: F401
 from .install import install, uninstall  # noqa: F401
 from .model.projection import set_lazy_surfaces  # noqa: F401
+from .model.extrinsics_regressed import ExtrinsicsRegressed, ExtrinsicsRegressedCfg  # noqa: F401
 from .graph import GraphedShardedStep, GraphedStep  # noqa: F401
 from .host import freeze_gc  # noqa: F401
 from ._ops import release_flow_originals  # noqa: F401
@@ -27,5 +28,5 @@ from .types import BackboneOutput, Batch, Flows, ModelOutput, Tracks  # noqa: F4
 
 __all__ = [
     "config", "loss", "model", "install", "uninstall", "set_lazy_surfaces", "FusedAdam", "GraphedStep", "GraphedShardedStep", "freeze_gc", "release_flow_originals",
-    "Batch", "BackboneOutput", "Flows", "ModelOutput", "Tracks",
+    "Batch", "BackboneOutput", "Flows", "ModelOutput", "Tracks", "ExtrinsicsRegressed", "ExtrinsicsRegressedCfg",
 ]

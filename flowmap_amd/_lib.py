@@ -114,6 +114,8 @@ SIGNATURES = {
     "fm_flow_pack_inputs_bitmask": [P, P, P, P, I, I, I, I, P, P],
     "fm_flow_pack_inputs_bitmask_views": [P, P, P, P, I, I, I, I, P, P, P],
     "fm_flow_loss_fused_bitmask": [P] * 7 + [I, I, I, I, I, F, F, F, P, P, I, P, P, P, P, P, L, D, D, D, D, P],
+    "fm_quat_pose_fwd": [P, P, I, P, P, P, P],
+    "fm_quat_pose_bwd": [P, P, P, P, P, P, I, P, P, P],
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -231,7 +231,7 @@ def _dense_flow_is_rough(bwd_flow: Tensor, h: int, w: int) -> bool:
 
 # which backward path the facades selected (tests)
 counters = {"procrustes_planned": 0, "procrustes_dense_planned": 0, "flow_packs": 0, "flow_packs_bitmask": 0, "procrustes_plans_built": 0, "track_tap_samples": 0,
-            "flow_tap_passes": 0, "flow_tap_absorbs": 0}
+            "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0}
 
 
 class LeadingFrames:
@@ -294,6 +294,47 @@ class AllPairsPoses(torch.autograd.Function):
         with _guard(ext.device):
             call("fm_allpairs_pose_bwd", ptr(ext), ptr(g_rel), b, f, ptr(g_ext), stream_for(ext))
         return g_ext
+
+
+class QuaternionPoses(torch.autograd.Function):
+    """ExtrinsicsRegressed.forward (flowmap/model/extrinsics/extrinsics_regressed.py:17-39,72-83) in one launch, its backward in one:
+    rotations (P,4) as (i, j, k, r), translations (P,3) -> rel (1,P,4,4) = [[R, t], [0, 1]] (later camera -> earlier camera, what
+    get_extrinsics chains), rel_inv (1,P,4,4) = its inverse, and — ``want_extrinsics`` — the chain (1,P+1,4,4) from the same launch
+    (else None).  A gradient of the chain goes through fm_pose_chain_bwd first and enters the backward launch as a further dL/drel."""
+
+    @staticmethod
+    def forward(ctx, rotations: Tensor, translations: Tensor, want_extrinsics: bool):
+        check_device(rotations, translations)
+        quat, trans = _f32c(rotations, "rotations"), _f32c(translations, "translations")
+        pairs = quat.shape[0]
+        if quat.dim() != 2 or quat.shape[1] != 4 or tuple(trans.shape) != (pairs, 3) or pairs < 1:
+            raise RuntimeError(f"flowmap_amd: rotations (P,4) and translations (P,3) expected, got {tuple(quat.shape)} and {tuple(trans.shape)}")
+        rel = torch.empty((1, pairs, 4, 4), dtype=torch.float32, device=quat.device)
+        rel_inv = torch.empty_like(rel)
+        ext = torch.empty((1, pairs + 1, 4, 4), dtype=torch.float32, device=quat.device) if want_extrinsics else None
+        with _guard(quat.device):
+            call("fm_quat_pose_fwd", ptr(quat), ptr(trans), pairs, ptr(rel), ptr(rel_inv), ptr(ext), stream_for(quat))
+        counters["quat_pose_fwd"] += 1
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(quat, trans, rel, rel_inv, ext)
+        return rel, rel_inv, ext
+
+    @staticmethod
+    def backward(ctx, g_rel, g_rel_inv, g_ext):
+        quat, trans, rel, rel_inv, ext = ctx.saved_tensors
+        pairs = quat.shape[0]
+        g_rel = None if g_rel is None else _f32c(g_rel, "grad")
+        g_rel_inv = None if g_rel_inv is None else _f32c(g_rel_inv, "grad")
+        g_quat, g_trans = torch.empty_like(quat), torch.empty_like(trans)
+        with _guard(quat.device):
+            g_chain = None
+            if g_ext is not None and ext is not None:
+                g_chain = torch.empty_like(rel)
+                call("fm_pose_chain_bwd", ptr(rel), ptr(ext), ptr(_f32c(g_ext, "grad")), 1, pairs, ptr(g_chain), stream_for(quat))
+            call("fm_quat_pose_bwd", ptr(quat), ptr(trans), ptr(rel_inv), ptr(g_rel), ptr(g_rel_inv), ptr(g_chain), pairs, ptr(g_quat), ptr(g_trans),
+                 stream_for(quat))
+        counters["quat_pose_bwd"] += 1
+        return g_quat, g_trans, None
 
 
 # --------------------------------------------------------------------------------------

@@ -102,6 +102,47 @@ __device__ __forceinline__ void block_accumulate(const float (&v)[NV], double* l
   __syncthreads();
 }
 
+// The same chain by ONE wave in registers (round 5): the caller lets only threads 0..63 in.  The Hillis-Steele rounds exchange the 16 doubles
+// with wave shuffles instead of going through LDS between block-wide barriers — in the one-block-per-pair fit the barriers of a 1024-thread
+// block, eight of them, were most of the chain's 8-10 us (profiles/r04_fit_phase_clocks_*.txt: 7.6 us for 19 poses, 10 for 149).  Same
+// products in the same order as fm_procrustes.hip's pose_chain_by_wave0: chunk products, inclusive scan over the 64 chunks, re-walk — bit-identical results.
+__device__ __forceinline__ void pose_chain_one_wave(const float* r, int steps, float* e) {
+  const int t = threadIdx.x;  // the lane
+  const int chunk = (steps + 63) / 64;
+  const int lo = t * chunk, hi = min(steps, lo + chunk);
+  double prod[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  for (int s = lo; s < hi; ++s) {
+    double m[16], nxt[16];
+    for (int k = 0; k < 16; ++k) m[k] = r[(size_t)s * 16 + k];
+    mat4_mul(prod, m, nxt);
+    for (int k = 0; k < 16; ++k) prod[k] = nxt[k];
+  }
+  for (int off = 1; off < 64; off <<= 1) {
+    double left[16], out[16];
+    for (int k = 0; k < 16; ++k) left[k] = __shfl_up(prod[k], off, 64);
+    mat4_mul(left, prod, out);
+    if (t >= off)
+      for (int k = 0; k < 16; ++k) prod[k] = out[k];
+  }
+  double run[16];
+  for (int k = 0; k < 16; ++k) run[k] = __shfl_up(prod[k], 1, 64);  // the product of every chunk before this lane's
+  if (t == 0) {
+    for (int k = 0; k < 16; ++k) {
+      run[k] = (k % 5 == 0) ? 1.0 : 0.0;
+      e[k] = (float)run[k];  // E_0 = I
+    }
+  }
+  for (int s = lo; s < hi; ++s) {
+    double m[16], nxt[16];
+    for (int k = 0; k < 16; ++k) m[k] = r[(size_t)s * 16 + k];
+    mat4_mul(run, m, nxt);
+    for (int k = 0; k < 16; ++k) {
+      run[k] = nxt[k];
+      e[(size_t)(s + 1) * 16 + k] = (float)nxt[k];
+    }
+  }
+}
+
 }  // namespace fm
 
 #define FM_OK 0

@@ -1240,4 +1240,5 @@ FM_HD void dense_bwd_s(const DenseBwd& c, const float h[3], const float t[3], co
 // takes the bit-mask entry points of the fused flow loss from here, written over the fp32-format entry points it defines itself.
 #if !defined(__HIPCC__)
 #include "fm_flow_bitmask_host.h"
+#include "fm_extrinsics_host.h"
 #endif

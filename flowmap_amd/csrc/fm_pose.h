@@ -138,6 +138,117 @@ FM_HD void pose_chain_bwd_one(const float* rel, const float* e, const float* ge,
   }
 }
 
+// ---- ExtrinsicsRegressed (extrinsics_regressed.py:17-39,78-81): one pair's pose from a quaternion and a translation --------
+//   q = (i, j, k, r), NOT normalised:  s = 2 / (|q|² + 1e-8),  R = I + s·B(q),
+//   B = [ −(jj+kk)   ij − kr    ik + jr ]
+//       [  ij + kr  −(ii+kk)    jk − ir ]
+//       [  ik − jr   jk + ir   −(ii+jj) ]
+// The products are never contracted into FMAs: a host build (contraction off) and the device round every entry alike, so the
+// float matrices agree bit for bit.
+FM_HD void quat_rotation(const double* q, double* B, double* R, double* s_out) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double i = q[0], j = q[1], k = q[2], r = q[3];
+  const double n = ((i * i + j * j) + k * k) + r * r + 1e-8;
+  const double s = 2.0 / n;
+  B[0] = -(j * j + k * k);
+  B[1] = i * j - k * r;
+  B[2] = i * k + j * r;
+  B[3] = i * j + k * r;
+  B[4] = -(i * i + k * k);
+  B[5] = j * k - i * r;
+  B[6] = i * k - j * r;
+  B[7] = j * k + i * r;
+  B[8] = -(i * i + j * j);
+  for (int a = 0; a < 9; ++a) {
+    const double sb = s * B[a];
+    R[a] = (a % 4 == 0 ? 1.0 : 0.0) + sb;
+  }
+  *s_out = s;
+}
+
+// (quat_pose_fwd_one, quat_pose_bwd_one and pose_chain_fwd_one are DECLARED once more in fm_extrinsics_host.h, which a host build reaches
+// through fm_math.h before this file: a change of signature here is made there too.)
+//   tf = [[R, t], [0, 1]] (the matrix get_extrinsics chains: later camera -> earlier camera);  tf_inv = tf⁻¹ = [[R⁻¹, −R⁻¹t], [0, 1]] with
+//   R⁻¹ = adj(R)/det(R): R is orthogonal only up to the 1e-8 in s, and the reference's consumers invert it with linalg.inv.
+FM_HD void quat_pose_fwd_one(const float* q, const float* t, float* tf, float* tf_inv) {
+  const double qd[4] = {q[0], q[1], q[2], q[3]};
+  double B[9], R[9], s;
+  quat_rotation(qd, B, R, &s);
+  for (int a = 0; a < 3; ++a) {
+    for (int c = 0; c < 3; ++c) tf[a * 4 + c] = (float)R[a * 3 + c];
+    tf[a * 4 + 3] = t[a];
+  }
+  tf[12] = tf[13] = tf[14] = 0.f;
+  tf[15] = 1.f;
+  double adj[9];
+  adj[0] = R[4] * R[8] - R[5] * R[7];
+  adj[1] = R[2] * R[7] - R[1] * R[8];
+  adj[2] = R[1] * R[5] - R[2] * R[4];
+  adj[3] = R[5] * R[6] - R[3] * R[8];
+  adj[4] = R[0] * R[8] - R[2] * R[6];
+  adj[5] = R[2] * R[3] - R[0] * R[5];
+  adj[6] = R[3] * R[7] - R[4] * R[6];
+  adj[7] = R[1] * R[6] - R[0] * R[7];
+  adj[8] = R[0] * R[4] - R[1] * R[3];
+  const double inv_det = 1.0 / (R[0] * adj[0] + R[1] * adj[3] + R[2] * adj[6]);
+  for (int a = 0; a < 3; ++a) {
+    double ti = 0;
+    for (int c = 0; c < 3; ++c) {
+      const double v = adj[a * 3 + c] * inv_det;
+      tf_inv[a * 4 + c] = (float)v;
+      ti -= v * (double)t[c];
+    }
+    tf_inv[a * 4 + 3] = (float)ti;
+  }
+  tf_inv[12] = tf_inv[13] = tf_inv[14] = 0.f;
+  tf_inv[15] = 1.f;
+}
+
+// Backward of quat_pose_fwd_one.  g_tf / g_tf_inv: dL/dtf, dL/dtf⁻¹ (4x4 row-major, bottom rows ignored as in pose_solve_bwd_one; either may
+// be null); g_tf_more: a second dL/dtf (what the pose chain's backward produced; may be null).  dL/dtf⁻¹ enters as −tf⁻ᵀ·G·tf⁻ᵀ.
+FM_HD void quat_pose_bwd_one(const float* q, const float* t, const float* tf_inv, const float* g_tf, const float* g_tf_inv, float* g_q,
+                             float* g_t, const float* g_tf_more = nullptr) {
+  (void)t;
+  double G[16];
+  for (int a = 0; a < 16; ++a) G[a] = 0.0;
+  if (g_tf_inv) {
+    double inv[16], g[16], tmp[16];
+    for (int a = 0; a < 16; ++a) {
+      inv[a] = tf_inv[a];
+      g[a] = a < 12 ? (double)g_tf_inv[a] : 0.0;
+    }
+    mat4_mul_tn(inv, g, tmp);
+    mat4_mul_nt(tmp, inv, g);
+    for (int a = 0; a < 12; ++a) G[a] = -g[a];
+  }
+  for (int a = 0; a < 12; ++a) G[a] += (g_tf ? (double)g_tf[a] : 0.0) + (g_tf_more ? (double)g_tf_more[a] : 0.0);
+  const double qd[4] = {q[0], q[1], q[2], q[3]};
+  double B[9], R[9], s;
+  quat_rotation(qd, B, R, &s);
+  double gR[9], gs = 0;
+  for (int a = 0; a < 3; ++a)
+    for (int c = 0; c < 3; ++c) {
+      gR[a * 3 + c] = G[a * 4 + c];
+      gs += gR[a * 3 + c] * B[a * 3 + c];
+    }
+  const double i = qd[0], j = qd[1], k = qd[2], r = qd[3];
+  // dB/dq, entry by entry
+  const double di = j * (gR[1] + gR[3]) + k * (gR[2] + gR[6]) + r * (gR[7] - gR[5]) - 2.0 * i * (gR[4] + gR[8]);
+  const double dj = i * (gR[1] + gR[3]) + k * (gR[5] + gR[7]) + r * (gR[2] - gR[6]) - 2.0 * j * (gR[0] + gR[8]);
+  const double dk = i * (gR[2] + gR[6]) + j * (gR[5] + gR[7]) + r * (gR[3] - gR[1]) - 2.0 * k * (gR[0] + gR[4]);
+  const double dr = i * (gR[7] - gR[5]) + j * (gR[2] - gR[6]) + k * (gR[3] - gR[1]);
+  const double ds = -s * s * gs;  // ds/dq_a = −s²·q_a
+  g_q[0] = (float)(s * di + ds * i);
+  g_q[1] = (float)(s * dj + ds * j);
+  g_q[2] = (float)(s * dk + ds * k);
+  g_q[3] = (float)(s * dr + ds * r);
+  g_t[0] = (float)G[3];
+  g_t[1] = (float)G[7];
+  g_t[2] = (float)G[11];
+}
+
 // ---- relative poses with a GENERAL 4x4 inverse (projection.py:154,176) -----------------
 //   fwd = inv(E1)·E0    bwd = inv(E0)·E1     (e01 points at E0; E1 follows)
 FM_HD void relative_pose_fwd_one(const float* e01, float* fwd, float* bwd) {

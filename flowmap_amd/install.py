@@ -46,7 +46,7 @@ _CROPPING_SITES = ("flowmap.overfit", "flowmap.model.model_wrapper_pretrain")
 
 def install(lazy_surfaces: bool = True, fused_softmin: bool = True, flow_postprocess: bool = True, fused_adam: bool = True,
             cropping: bool = True, fused_regressed: bool = True, lazy_backbone: bool = True, graph: bool | None = None,
-            options: dict | None = None) -> None:
+            options: dict | None = None, fused_extrinsics_regressed: bool = True) -> None:
     """Patch the reference in place.  ``lazy_surfaces=True`` additionally lets
     ``Model.forward``'s ``unproject`` hand a LazySurfaces to the fused consumers;
     ``fused_softmin=True`` registers the fused candidate sweep as INTRINSICS["softmin"]
@@ -63,7 +63,9 @@ def install(lazy_surfaces: bool = True, fused_softmin: bool = True, flow_postpro
     ``lazy_backbone=True`` registers BACKBONES["explicit_depth"] (flowmap/model/backbone/__init__.py:5-8) = ``flowmap_amd``'s
     BackboneExplicitDepth (same cfg, same parameter names ``depth`` / ``weights``: state_dict-compatible), whose forward hands the weight
     logits on unevaluated when ``lazy_surfaces`` is on (flowmap_amd/model/backbone.py) — the step an unmodified ``overfit.py`` then runs is
-    the step ``bench.py`` times; ``graph=True`` (default: the environment's ``FLOWMAP_AMD_GRAPH=1``, else off) rebinds
+    the step ``bench.py`` times; ``fused_extrinsics_regressed=True`` registers EXTRINSICS["regressed"] (flowmap/model/extrinsics/__init__.py:10-13) =
+    ``flowmap_amd``'s ExtrinsicsRegressed (same cfg, same parameter names ``rotations`` / ``translations``: one launch forward, one backward, and it
+    reads only the shape of the surfaces, so ``lazy_surfaces`` stays on); ``graph=True`` (default: the environment's ``FLOWMAP_AMD_GRAPH=1``, else off) rebinds
     ``ModelWrapperOverfit.training_step`` (model_wrapper_overfit.py:51-73) to a step that replays the model's forward + the losses and the
     loss's ``backward()`` as two hipGraphs while the optimisation's host-side control flow stands still, and runs the reference's own method
     otherwise (flowmap_amd/training.py: what the reference's default ≈ 180×240 resolution needs, where the eager step is host-bound; videos
@@ -127,7 +129,17 @@ def install(lazy_surfaces: bool = True, fused_softmin: bool = True, flow_postpro
         _reference.twins["Mapping:" + kind] = cls
     _set(ref_loss, "LOSSES", {**ref_loss.LOSSES, "flow": our_loss.LossFlow, "tracking": our_loss.LossTracking})
     _set(ref_mapping, "MAPPINGS", {**ref_mapping.MAPPINGS, **our_mapping.MAPPINGS})
-    _set(ref_extr, "EXTRINSICS", {**ref_extr.EXTRINSICS, "procrustes": ExtrinsicsProcrustes})
+    extrinsics_classes = [ExtrinsicsProcrustes]
+    registry = {**ref_extr.EXTRINSICS, "procrustes": ExtrinsicsProcrustes}
+    if fused_extrinsics_regressed:
+        from .model.extrinsics_regressed import ExtrinsicsRegressed
+
+        ref_regressed = ref_extr.EXTRINSICS.get("regressed")  # (a stand-in package's registry may have no such entry)
+        if ref_regressed is not None:
+            _reference.twins["ExtrinsicsRegressed"] = ref_regressed
+        registry["regressed"] = ExtrinsicsRegressed
+        extrinsics_classes.append(ExtrinsicsRegressed)
+    _set(ref_extr, "EXTRINSICS", registry)
     if fused_softmin:
         from .model.intrinsics_softmin import IntrinsicsSoftmin
 
@@ -157,7 +169,7 @@ def install(lazy_surfaces: bool = True, fused_softmin: bool = True, flow_postpro
     # The reference's factories are annotated with its abstract bases (`get_backbone(...) -> Backbone`, backbone/__init__.py:13-18; likewise
     # get_extrinsics / get_intrinsics / get_losses / get_mapping), which beartype checks under the import hook of overfit.py:15-19: the classes
     # registered above are declared virtual subclasses of those bases (ABCMeta.register; all four bases are ABCs).
-    for mod_name, base_name, ours in _virtual_bases(our_loss, our_mapping, ExtrinsicsProcrustes, fused_softmin, fused_regressed, lazy_backbone):
+    for mod_name, base_name, ours in _virtual_bases(our_loss, our_mapping, tuple(extrinsics_classes), fused_softmin, fused_regressed, lazy_backbone):
         try:
             base = getattr(importlib.import_module(mod_name), base_name)
             for cls in ours:
@@ -262,11 +274,11 @@ def install(lazy_surfaces: bool = True, fused_softmin: bool = True, flow_postpro
     our_projection.set_lazy_surfaces(lazy_surfaces)
 
 
-def _virtual_bases(our_loss, our_mapping, extrinsics_cls, fused_softmin, fused_regressed, lazy_backbone):
+def _virtual_bases(our_loss, our_mapping, extrinsics_classes, fused_softmin, fused_regressed, lazy_backbone):
     """(module, abstract base, this package's classes registered under it)."""
     out = [("flowmap.loss.loss", "Loss", (our_loss.LossFlow, our_loss.LossTracking)),
            ("flowmap.loss.mapping.mapping", "Mapping", tuple(our_mapping.MAPPINGS.values())),
-           ("flowmap.model.extrinsics.extrinsics", "Extrinsics", (extrinsics_cls,))]
+           ("flowmap.model.extrinsics.extrinsics", "Extrinsics", tuple(extrinsics_classes))]
     intrinsics = []
     if fused_softmin:
         from .model.intrinsics_softmin import IntrinsicsSoftmin

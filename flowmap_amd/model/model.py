@@ -19,6 +19,7 @@ from .. import _ops, _reference
 from ..types import ModelOutput
 from .backbone import BackboneExplicitDepth, BackboneExplicitDepthCfg  # noqa: F401  (flowmap/model/backbone/backbone_explicit_depth.py)
 from .extrinsics_procrustes import ExtrinsicsProcrustes, ExtrinsicsProcrustesCfg
+from .extrinsics_regressed import ExtrinsicsRegressed, ExtrinsicsRegressedCfg
 from .projection import sample_image_grid, unproject
 
 
@@ -80,7 +81,7 @@ class ModelCfg:
 
     backbone: BackboneExplicitDepthCfg
     intrinsics: "IntrinsicsRegressedCfg | IntrinsicsSoftminCfg"
-    extrinsics: ExtrinsicsProcrustesCfg
+    extrinsics: "ExtrinsicsProcrustesCfg | ExtrinsicsRegressedCfg"
     use_correspondence_weights: bool = True
 
 
@@ -97,7 +98,10 @@ class Model(nn.Module):
             self.intrinsics = IntrinsicsSoftmin(cfg.intrinsics)
         else:
             self.intrinsics = IntrinsicsRegressed(cfg.intrinsics)
-        self.extrinsics = ExtrinsicsProcrustes(cfg.extrinsics, num_frames)
+        if cfg.extrinsics.name == "regressed":  # model/extrinsics/__init__.py:10-13 registry, two entries
+            self.extrinsics = ExtrinsicsRegressed(cfg.extrinsics, num_frames)
+        else:
+            self.extrinsics = ExtrinsicsProcrustes(cfg.extrinsics, num_frames)
 
     def forward(self, batch, flows, global_step: int) -> ModelOutput:
         device = batch.videos.device

@@ -126,7 +126,15 @@ class FrameShard:
           regressed focal length is an ordinary shared parameter (sync() all-reduces its gradient).
         * The halo exchange of dL/ddepth starts from a gradient hook, as soon as that gradient is final.
         * The depth parameter is told which of its frames are shared with a neighbour (``_fm_halo_frames``): an in-pass
-          optimiser update (FusedAdam.fuse_depth_update) leaves those frames to a dense update after the exchange."""
+          optimiser update (FusedAdam.fuse_depth_update) leaves those frames to a dense update after the exchange.
+
+        Frame sharding chains the poses of the Procrustes fit across ranks; a model with regressed extrinsics (one parameter row per pair of
+        the WHOLE video) is refused by name."""
+        from .model.extrinsics_regressed import ExtrinsicsRegressed
+
+        if self.world > 1 and isinstance(getattr(model, "extrinsics", None), ExtrinsicsRegressed):
+            raise ValueError("flowmap_amd: frame sharding needs Procrustes extrinsics; this model's extrinsics module is ExtrinsicsRegressed "
+                             "(extrinsics: regressed), whose per-pair parameters are not split over ranks")
         if not self.active:
             return
         from .model.intrinsics_softmin import IntrinsicsSoftmin

@@ -12,8 +12,8 @@ the caller's and runs eagerly.
 What a replay cannot see is host-side control flow, so the graphs exist only while that control flow is constant — the PHASE of the
 optimisation — and every call checks it:
 
-* every part of the model and every loss is a class of this package (a reference backbone such as MiDaS, a regressed-extrinsics module or
-  a foreign loss keeps the reference's eager ``training_step``);
+* every part of the model and every loss is a class of this package (a reference backbone such as MiDaS, the reference's own regressed-extrinsics
+  module or a foreign loss keeps the reference's eager ``training_step``);
 * every loss is switched on (``global_step >= cfg.enable_after``, loss/loss.py:39-41) and the intrinsics module is past its hand-over
   (intrinsics_softmin.py:74-82: the softmin sweep records focal lengths on the host until ``regression.after_step``);
 * tensors on the GPU, the HIP library loaded, gradients enabled, module in training mode, the same batch / flows / tracks objects, the same
@@ -104,10 +104,11 @@ def _our_classes():
         from .loss import LossFlow, LossTracking
         from .model.backbone import BackboneExplicitDepth
         from .model.extrinsics_procrustes import ExtrinsicsProcrustes
+        from .model.extrinsics_regressed import ExtrinsicsRegressed
         from .model.intrinsics_softmin import IntrinsicsSoftmin
         from .model.model import IntrinsicsRegressed
 
-        _classes = (BackboneExplicitDepth, ExtrinsicsProcrustes, IntrinsicsSoftmin, IntrinsicsRegressed, (LossFlow, LossTracking))
+        _classes = (BackboneExplicitDepth, (ExtrinsicsProcrustes, ExtrinsicsRegressed), IntrinsicsSoftmin, IntrinsicsRegressed, (LossFlow, LossTracking))
     return _classes
 
 

@@ -40,8 +40,9 @@ extern "C" {
  * points fm_flow_loss_fused_taps / fm_track_loss_fused_fwd_taps / fm_tap_grad_apply; round 5, version 5: fm_tap_grad_apply reports a
  * non-zero correction through a device flag; fm_track_presample and the `presampled` argument of fm_track_loss_fused_fwd_taps; round 6,
  * version 6: that entry point and that argument are gone again — measured, not adopted: docs/history/patches/r05_track_presample.patch; version 7: the bit-mask packed format of the fused flow
- * loss — fm_flow_masks_binary, fm_flow_pack_inputs_bitmask(_views), fm_flow_loss_fused_bitmask; the existing entries are unchanged).  A binding checks fm_abi_version() == FM_ABI_VERSION when it loads the library. */
-#define FM_ABI_VERSION 7
+ * loss — fm_flow_masks_binary, fm_flow_pack_inputs_bitmask(_views), fm_flow_loss_fused_bitmask; the existing entries are unchanged; version 8: the regressed
+ * extrinsics — fm_quat_pose_fwd / fm_quat_pose_bwd; the existing entries are unchanged).  A binding checks fm_abi_version() == FM_ABI_VERSION when it loads the library. */
+#define FM_ABI_VERSION 8
 int fm_abi_version(void);
 
 #define FM_STAT_STRIDE 16      /* doubles per pair in `stats` */
@@ -699,6 +700,27 @@ int fm_flow_loss_fused_bitmask(float* depth, const float* k, const float* kinv, 
                                float aspect_y, float* grad_depth, double* acc, int items_per_thread, const fm_layout* depth_layout,
                                const fm_flow_taps* taps, float* exp_avg, float* exp_avg_sq, const uint8_t* touched, long step, double lr, double beta1,
                                double beta2, double eps, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Regressed extrinsics (ABI version 8).  ExtrinsicsRegressed.forward (flowmap/model/extrinsics/extrinsics_regressed.py:17-39,72-83):
+ * per-pair quaternion + translation parameters -> 4x4 poses, chained by get_extrinsics (projection.py:187-210).
+ *
+ *   quat (pairs,4) in the order (i, j, k, r), NOT normalised: R = I + s·B(q) with s = 2 / (|q|² + 1e-8); trans (pairs,3).
+ *   t_bwd (pairs,4,4) out = [[R, t], [0, 1]]: later camera -> earlier camera, the factor get_extrinsics chains;
+ *   t_fwd (pairs,4,4) out = its TRUE inverse (3x3 adjugate in fp64: R is orthogonal only up to the 1e-8 in s) —
+ *          the (t_bwd, t_fwd) of fm_procrustes_fit, so the fused flow loss reads both directly;
+ *   ext (pairs+1,4,4) out, or NULL: ext[0] = I, ext[k] = ext[k-1]·t_bwd[k-1], chained in the SAME launch by one wave of
+ *          the last workgroup to finish (as fm_procrustes_fit_chain does).  One batch element (the reference asserts b == 1).
+ * One launch each, one thread per pair, workgroups of 256.  With more than 256 pairs and ext != NULL the forward counts its
+ * finished workgroups in a device-global counter that it leaves zero: such launches on one device must be ordered by their
+ * streams (two of them running concurrently on different streams is not supported).
+ *
+ * fm_quat_pose_bwd: t_fwd as the forward wrote it; g_t_bwd / g_t_fwd (pairs,4,4): dL/dt_bwd, dL/dt_fwd, bottom rows ignored,
+ *   either may be NULL (no gradient); g_rel_chain (pairs,4,4) or NULL: a further dL/dt_bwd — what fm_pose_chain_bwd produced
+ *   from dL/dext.  EVERY element of g_quat (pairs,4) and g_trans (pairs,3) is written (no zero fill beforehand).  fp64 inside. */
+int fm_quat_pose_fwd(const float* quat, const float* trans, int pairs, float* t_bwd, float* t_fwd, float* ext, void* stream);
+int fm_quat_pose_bwd(const float* quat, const float* trans, const float* t_fwd, const float* g_t_bwd, const float* g_t_fwd,
+                     const float* g_rel_chain, int pairs, float* g_quat, float* g_trans, void* stream);
 
 #ifdef __cplusplus
 }
