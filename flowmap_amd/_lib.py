@@ -116,6 +116,8 @@ SIGNATURES = {
     "fm_flow_loss_fused_bitmask": [P] * 7 + [I, I, I, I, I, F, F, F, P, P, I, P, P, P, P, P, L, D, D, D, D, P],
     "fm_quat_pose_fwd": [P, P, I, P, P, P, P],
     "fm_quat_pose_bwd": [P, P, P, P, P, P, I, P, P, P],
+    "fm_flow_residual_blocks": [I, I, P],
+    "fm_flow_residuals": [P] * 9 + [I, I, I, I, I, F, F, F, I, I] + [P] * 9,
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -231,7 +231,7 @@ def _dense_flow_is_rough(bwd_flow: Tensor, h: int, w: int) -> bool:
 
 # which backward path the facades selected (tests)
 counters = {"procrustes_planned": 0, "procrustes_dense_planned": 0, "flow_packs": 0, "flow_packs_bitmask": 0, "procrustes_plans_built": 0, "track_tap_samples": 0,
-            "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0}
+            "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0, "flow_residuals": 0}
 
 
 class LeadingFrames:
@@ -713,6 +713,18 @@ class FlowLossFused:
             if dense is not None:
                 early.start_early_halo(dense, _root(depth), (t_fwd, t_bwd, k, kinv, norm, int(kind), float(delta)))
         return as_root_loss(loss)
+
+
+def flow_residuals(depth, k, t_fwd, t_bwd, flow_fwd, flow_bwd, mask_fwd, mask_bwd, kind, delta, first_pair, count, predicted_flow, sums):
+    """The per-pixel flow terms of the pairs [first_pair, first_pair + count) straight from depth (csrc/fm_torch.cpp: flow_residuals_op ->
+    fm_flow_residuals): (residual_fwd, residual_bwd, pred_fwd, pred_bwd, pair_sum, pair_valid), None for what was not asked for.  One
+    launch, plus the ordered second stage of the sums.  Reads its arguments and nothing else: no DepthSink, no tap plan, no optimiser
+    ticket, no note on any tensor beyond the cached K^-1 the fused loss keeps as well."""
+    kinv = intrinsics_inverse(k)
+    out = torch_ops().flow_residuals(depth, k, kinv, t_fwd, t_bwd, flow_fwd, flow_bwd, mask_fwd, mask_bwd, int(kind), float(delta), int(first_pair),
+                                     int(count), bool(predicted_flow), bool(sums))
+    counters["flow_residuals"] += 1
+    return tuple(x if x.numel() else None for x in out)
 
 
 def softmin_intrinsics(depth, weights, bwd_flow, indices, candidate_k, rel, weight_sens, frames):

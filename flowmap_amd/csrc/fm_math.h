@@ -456,6 +456,56 @@ FM_HD void flow_term_fast(const DirConst& d, float arow, float brow, float crow,
 }
 
 // ---------------------------------------------------------------------------------
+// One pixel of LossFlow.residuals (fm_flow_residuals.hip; the host build runs the same code): the UNMASKED flow term ρ of the fused
+// pass — flow_term_fast with mask 1 and no gradient, so the value is the hot path's own — and the pose-induced flow xy_flowed − xy
+// it is the mapping of, recovered from the same pu, pv (kd is pre-scaled by the aspect factors: xy_flowed = (pu / ax, pv / ay)).
+// The fused pass DROPS a pixel whose Z'+1e-5 is not invertible (its mask is zeroed); a per-pixel map has to show it, so such a pixel
+// takes the function-level route with the reference's exact clamp semantics (project_point: ±1e8 / NaN -> 0, then the mapping of
+// fm_mapping_fwd).  pose44 / kinv9 / kdst9: the pair's pose and the two intrinsics, read only on that route.
+// ---------------------------------------------------------------------------------
+struct FlowResidual {
+  float rho;     // mapping.forward(xy_flowed − xy, flow, (h, w)), before the mask
+  float fx, fy;  // xy_flowed − xy
+};
+
+template <int KIND>
+FM_HD FlowResidual flow_residual_at(const DirConst& d, float arow, float brow, float crow, float z, float u, float v, float u_ax, float v_ay,
+                                    float flow_x, float flow_y, float delta, float inv_delta, float ax, float ay, float inv_ax, float inv_ay,
+                                    const float* pose44, const float* kinv9, const float* kdst9) {
+  float acc[kFlowAcc];
+  for (int i = 0; i < kFlowAcc; ++i) acc[i] = 0.f;
+  float gz = 0.f;
+  flow_term_fast<KIND, false>(d, arow, brow, crow, z, u, z * u, z * v, u_ax, v_ay, flow_x, flow_y, 1.f, 0.f, delta, inv_delta, ax, ay, acc, gz);
+  // pu, pv and the test of q exactly as flow_term_fast forms them (the same expressions: the compiler keeps one copy)
+  const float a = fmaf(d.au, u, arow);
+  const float b = fmaf(d.bu, u, brow);
+  const float c = fmaf(d.cu, u, crow);
+  const float q = fm_rcp(fmaf(z, c, d.tc) + kProjEps);
+  FlowResidual o;
+  if (fabsf(q) <= 3.0e38f) {
+    o.rho = acc[0];
+    o.fx = fmaf(fmaf(z, a, d.ta) * q, inv_ax, -u);
+    o.fy = fmaf(fmaf(z, b, d.tb) * q, inv_ay, -v);
+    return o;
+  }
+  Mat3 ki, kd;
+  Pose t;
+  load_mat3(kinv9, ki);
+  load_mat3(kdst9, kd);
+  load_pose44(pose44, t);
+  float ray[3], x[3], xc[3];
+  ray_dir(ki, u, v, ray);
+  for (int i = 0; i < 3; ++i) x[i] = ray[i] * z;
+  apply_pose(t, x, xc);
+  const Projected pr = project_point(xc, kd);
+  o.fx = pr.u - u;
+  o.fy = pr.v - v;
+  float dx, dy;
+  o.rho = robust_map(KIND, delta, aspect_diff(o.fx, flow_x, ax), aspect_diff(o.fy, flow_y, ay), dx, dy);
+  return o;
+}
+
+// ---------------------------------------------------------------------------------
 // One (candidate, sampled pixel) term of IntrinsicsSoftmin's score (intrinsics_softmin.py:105-121):
 //   X = z·K⁻¹[u,v,1] (unproject the later frame's pixel), X' = T·X (fitted pose, later -> earlier),
 //   xy = project_camera_space(X', K) (exact ±1e8 / NaN->0 semantics), flow = xy − (u,v),
@@ -1241,4 +1291,5 @@ FM_HD void dense_bwd_s(const DenseBwd& c, const float h[3], const float t[3], co
 #if !defined(__HIPCC__)
 #include "fm_flow_bitmask_host.h"
 #include "fm_extrinsics_host.h"
+#include "fm_flow_residuals_host.h"
 #endif

@@ -50,7 +50,7 @@ using OptTensor = std::optional<Tensor>;
   X(fm_depth_gather) X(fm_extrinsics_inverse) X(fm_track_loss_fused_fwd) X(fm_track_loss_bwd) X(fm_adam_step)                 \
   X(fm_adam_step_capturable) X(fm_softmin_score_fwd) X(fm_softmin_score_bwd) X(fm_softmin_blend_fwd) X(fm_softmin_blend_bwd)         \
   X(fm_random_subset) X(fm_random_subset_stateful) X(fm_abi_version) X(fm_flow_loss_fused_taps) X(fm_track_loss_fused_fwd_taps) X(fm_tap_grad_apply) \
-  X(fm_flow_loss_fused_bitmask)
+  X(fm_flow_loss_fused_bitmask) X(fm_flow_residuals) X(fm_flow_residual_blocks)
 
 struct Api {
 #define X(name) decltype(&::name) name = nullptr;
@@ -1511,6 +1511,62 @@ static Tensor leading_frames_op(const Tensor& x, int64_t count, const OptSink& s
   return LeadingFrames::apply(x, count, sink_of(sink));
 }
 
+// LossFlow.residuals on lazy surfaces (fm_flow_residuals): the per-pixel flow terms of a window of pairs, optionally the pose-induced flows
+// and the per-pair masked sums, straight from depth.  Not differentiable: plain tensors that require no gradient.  -> {residual_fwd,
+// residual_bwd, pred_fwd, pred_bwd, pair_sum, pair_valid}; what was not asked for comes back as an empty tensor.
+static std::vector<Tensor> flow_residuals_op(const Tensor& depth_in, const Tensor& k_in, const Tensor& kinv_in, const Tensor& t_fwd_in, const Tensor& t_bwd_in,
+                                             const Tensor& flow_fwd_in, const Tensor& flow_bwd_in, const Tensor& mask_fwd_in, const Tensor& mask_bwd_in,
+                                             int64_t kind, double delta, int64_t first_pair, int64_t count, bool predicted_flow, bool sums) {
+  at::NoGradGuard no_grad;
+  check_device({&depth_in, &k_in, &kinv_in, &t_fwd_in, &t_bwd_in, &flow_fwd_in, &flow_bwd_in, &mask_fwd_in, &mask_bwd_in});
+  TORCH_CHECK(flow_fwd_in.scalar_type() == at::kFloat && flow_bwd_in.scalar_type() == at::kFloat && mask_fwd_in.scalar_type() == at::kFloat &&
+                  mask_bwd_in.scalar_type() == at::kFloat,
+              "flowmap_amd: flows and masks must be float32");
+  const ImageStack stacks[5] = {image_stack(depth_in.detach(), "depth"), image_stack(flow_fwd_in, "forward flow"), image_stack(flow_bwd_in, "backward flow"),
+                                image_stack(mask_fwd_in, "forward mask"), image_stack(mask_bwd_in, "backward mask")};
+  const Tensor &depth = stacks[0].t, &flow_fwd = stacks[1].t, &flow_bwd = stacks[2].t, &mask_fwd = stacks[3].t, &mask_bwd = stacks[4].t;
+  const Tensor k = f32c(k_in.detach(), "intrinsics"), kinv = f32c(kinv_in.detach(), "inverse intrinsics");
+  const Tensor t_fwd = f32c(t_fwd_in.detach(), "forward poses"), t_bwd = f32c(t_bwd_in.detach(), "backward poses");
+  TORCH_CHECK(depth.dim() == 4, "flowmap_amd: depth must be (batch, frame, height, width)");
+  const int64_t b = depth.size(0), f = depth.size(1), h = depth.size(2), w = depth.size(3);
+  TORCH_CHECK(h * w < (int64_t(1) << 30), "flowmap_amd: the flow residuals index pixels inside a frame with 32 bits: height x width = ", h * w,
+              " must stay below 2^30 (frames x height x width is not limited)");
+  TORCH_CHECK(flow_fwd.sizes() == at::IntArrayRef({b, f - 1, h, w, 2}) && flow_bwd.sizes() == flow_fwd.sizes(), "flowmap_amd: flow shape does not match depth");
+  TORCH_CHECK(mask_fwd.sizes() == at::IntArrayRef({b, f - 1, h, w}) && mask_bwd.sizes() == mask_fwd.sizes(), "flowmap_amd: mask shape does not match depth");
+  TORCH_CHECK(k.sizes() == at::IntArrayRef({b, f, 3, 3}) && kinv.sizes() == k.sizes() && t_fwd.sizes() == at::IntArrayRef({b, f - 1, 4, 4}) &&
+                  t_bwd.sizes() == t_fwd.sizes(),
+              "flowmap_amd: intrinsics / pose shapes do not match depth");
+  TORCH_CHECK(first_pair >= 0 && count >= 1 && first_pair + count <= f - 1, "flowmap_amd: the pair window [", first_pair, ", ", first_pair + count,
+              ") does not lie in the ", f - 1, " pairs");
+  TORCH_CHECK(b * count <= 65535, "flowmap_amd: the flow residuals handle at most 65 535 pairs per call (batch x pairs = ", b * count, "): split the window");
+  fm_layout lay[5];
+  bool any_view = false;
+  for (int i = 0; i < 5; ++i) {
+    lay[i] = stacks[i].lay;
+    any_view = any_view || stacks[i].is_view();
+  }
+  Tensor res_f = at::empty({b, count, h, w}, depth.options()), res_b = at::empty({b, count, h, w}, depth.options());
+  Tensor pred_f = at::empty({0}, depth.options()), pred_b = pred_f, pair_sum = at::empty({0}, depth.options().dtype(at::kDouble)), pair_valid = pair_sum, work;
+  if (predicted_flow) {
+    pred_f = at::empty({b, count, h, w, 2}, depth.options());
+    pred_b = at::empty({b, count, h, w, 2}, depth.options());
+  }
+  if (sums) {
+    int blocks = 0;
+    FM_CALL(fm_flow_residual_blocks, (int)h, (int)w, &blocks);
+    pair_sum = at::empty({b, count, 2}, depth.options().dtype(at::kDouble));
+    pair_valid = at::empty({b, count, 2}, depth.options().dtype(at::kDouble));
+    work = at::empty({b * count * 2 * (int64_t)blocks * 2}, depth.options().dtype(at::kDouble));
+  }
+  const float scale = std::sqrt((float)(h * w));
+  DeviceScope scope(depth.device());
+  FM_CALL(fm_flow_residuals, ptr(depth), ptr(k), ptr(kinv), ptr(t_fwd), ptr(t_bwd), ptr(flow_fwd), ptr(flow_bwd), ptr(mask_fwd), ptr(mask_bwd), (int)b, (int)f,
+          (int)h, (int)w, (int)kind, (float)delta, (float)w / scale, (float)h / scale, (int)first_pair, (int)count, ptr(res_f), ptr(res_b),
+          predicted_flow ? ptr(pred_f) : nullptr, predicted_flow ? ptr(pred_b) : nullptr, sums ? ptr<double>(pair_sum) : nullptr,
+          sums ? ptr<double>(pair_valid) : nullptr, sums ? ptr<double>(work) : nullptr, any_view ? lay : nullptr, scope.stream);
+  return {res_f, res_b, pred_f, pred_b, pair_sum, pair_valid};
+}
+
 }  // namespace fmt
 
 TORCH_LIBRARY(flowmap_amd, m) {
@@ -1586,4 +1642,7 @@ TORCH_LIBRARY(flowmap_amd, m) {
   m.def("view_copies() -> int", []() { return fmt::view_copy_counter(); });
   m.def("flow_timing_enable(bool on) -> ()", fmt::flow_timing_enable);
   m.def("flow_timing_collect(bool tracking) -> float[]", fmt::flow_timing_collect);
+  m.def("flow_residuals(Tensor depth, Tensor k, Tensor kinv, Tensor t_fwd, Tensor t_bwd, Tensor flow_fwd, Tensor flow_bwd, Tensor mask_fwd, Tensor mask_bwd, "
+        "int kind, float delta, int first_pair, int count, bool predicted_flow, bool sums) -> Tensor[]",
+        fmt::flow_residuals_op);
 }

@@ -8,8 +8,9 @@ from typing import Literal, Optional
 import torch
 from torch import Tensor
 
-from .. import _ops
-from ..model.projection import LazySurfaces, _dense_extrinsics, compute_backward_flow, compute_forward_flow, sample_image_grid
+from .. import _ops, _reference
+from ..types import FlowResiduals
+from ..model.projection import LazyExtrinsics, LazySurfaces, _dense_extrinsics, compute_backward_flow, compute_forward_flow, sample_image_grid
 from .loss import Loss, LossCfgCommon, or_one
 from .mapping import MappingCfg, get_mapping
 
@@ -114,3 +115,73 @@ class LossFlow(Loss[LossFlowCfg]):
         valid_sum = valid_sum + flows.backward_mask.sum()
 
         return loss_sum / or_one(valid_sum)
+
+    # -- per-pixel view ---------------------------------------------------------------------
+    @staticmethod
+    def _pair_window(pairs, total: int):
+        """``pairs`` of residuals() -> (first, count): None (all pairs), a slice with step 1, or (first, count)."""
+        if pairs is None:
+            first, count = 0, total
+        elif isinstance(pairs, slice):
+            if pairs.step not in (None, 1):
+                raise ValueError(f"flowmap_amd: LossFlow.residuals takes a slice of pairs with step 1 (got step {pairs.step})")
+            first, stop, _ = pairs.indices(total)
+            count = stop - first
+        elif isinstance(pairs, (tuple, list)) and len(pairs) == 2 and all(isinstance(x, int) and not isinstance(x, bool) for x in pairs):
+            first, count = pairs
+        else:
+            raise ValueError(f"flowmap_amd: LossFlow.residuals: pairs must be None, a slice with step 1 or (first, count), got {pairs!r}")
+        if first < 0 or count < 1 or first + count > total:
+            raise ValueError(f"flowmap_amd: LossFlow.residuals: the pairs [{first}, {first + count}) do not lie in the {total} pairs of the video")
+        return int(first), int(count)
+
+    def residuals(self, batch, flows, model_output, pairs=None, predicted_flow: bool = False, sums: bool = True) -> FlowResiduals:
+        """The per-pixel and per-pair quantities of ``compute_unweighted_loss`` (loss_flow.py:46-68) for the pairs ``pairs`` — None (all), a
+        slice with step 1, or (first, count): ``forward`` / ``backward`` = mapping.forward(xy_flowed − xy, flow, (h, w)) BEFORE the mask;
+        with ``predicted_flow`` the pose-induced flows xy_flowed − xy; with ``sums`` Σ residual·mask and Σ mask per pair and direction
+        in float64.  The forward term of pair i reads frame i's depth, the backward term frame i+1's.
+
+        On the model's own lazy surfaces (the fused loss's condition) this is ONE launch over depth (fm_flow_residuals, plus the small
+        ordered second stage of the sums) and nothing of size (b,f,h,w,3) exists; with an explicit surfaces tensor it composes the
+        general-path operators; host tensors after install() go to the reference's own functions.  Never differentiable, and it leaves
+        the training step alone: no look-ahead or fused-Adam state, no tap image, no note on the flow tensors."""
+        total = model_output.depths.shape[1] - 1
+        first, count = self._pair_window(pairs, total)
+        with torch.no_grad():
+            if self._fusable(model_output) and not _reference.on_host(batch):
+                return self._residuals_fused(flows, model_output, first, count, predicted_flow, sums)
+            return self._residuals_general(batch, flows, model_output, first, count, predicted_flow, sums)
+
+    def _residuals_fused(self, flows, model_output, first: int, count: int, predicted_flow: bool, sums: bool) -> FlowResiduals:
+        s: LazySurfaces = model_output.surfaces
+        ext = model_output.extrinsics
+        direct = getattr(ext, "_fm_relative_poses", None) if (self.use_fitted_poses or isinstance(ext, LazyExtrinsics)) else None
+        if direct is not None and direct[0].shape[:2] == (s.depths.shape[0], s.depths.shape[1] - 1):
+            rel_fwd, rel_bwd = direct
+        else:
+            rel_fwd, rel_bwd = _ops.RelativePoses.apply(_dense_extrinsics(ext).detach())
+        out = _ops.flow_residuals(s.depths.detach(), model_output.intrinsics.detach(), rel_fwd.detach(), rel_bwd.detach(), flows.forward, flows.backward,
+                                  flows.forward_mask, flows.backward_mask, _ops.MAPPING_KINDS[self.mapping.kind], self.mapping.delta, first, count,
+                                  predicted_flow, sums)
+        return FlowResiduals(*out, first)
+
+    def _residuals_general(self, batch, flows, model_output, first: int, count: int, predicted_flow: bool, sums: bool) -> FlowResiduals:
+        _, _, _, h, w = batch.videos.shape
+        # host tensors after install(): the reference's own functions (flowmap_amd/_reference.py); without install() ours refuse them
+        grid = _reference.host_twin("sample_image_grid", batch) or sample_image_grid
+        forward_flow = _reference.host_twin("compute_forward_flow", batch) or compute_forward_flow
+        backward_flow = _reference.host_twin("compute_backward_flow", batch) or compute_backward_flow
+        xy, _ = grid((h, w), batch.videos.device)
+        ext = model_output.extrinsics
+        if isinstance(ext, LazyExtrinsics):  # the chain for this call only: nothing is noted on the flow tensor
+            ext = ext._dense if ext._dense is not None else _ops.PoseChain.apply(ext._rel)
+        win, frames = slice(first, first + count), slice(first, first + count + 1)
+        surfaces, ext, k = model_output.surfaces[:, frames], ext[:, frames], model_output.intrinsics[:, frames]
+        fields = []
+        for positions, flow, mask in ((forward_flow, flows.forward, flows.forward_mask), (backward_flow, flows.backward, flows.backward_mask)):
+            pred = positions(surfaces, ext, k) - xy
+            res = self.mapping.forward(pred, flow[:, win], (h, w))
+            fields.append((res, pred, (res * mask[:, win]).to(torch.float64).sum(dim=(2, 3)), mask[:, win].to(torch.float64).sum(dim=(2, 3))))
+        (rf, pf, sf, vf), (rb, pb, sb, vb) = fields
+        return FlowResiduals(rf, rb, pf if predicted_flow else None, pb if predicted_flow else None, torch.stack((sf, sb), dim=-1) if sums else None,
+                             torch.stack((vf, vb), dim=-1) if sums else None, first)

@@ -5,6 +5,7 @@
   Batch        flowmap/dataset/types.py:12-19      (only .videos shape/device is read)
   ModelOutput  flowmap/model/model.py:24-30
   BackboneOutput  flowmap/model/backbone/backbone.py:14-17
+  FlowResiduals  what LossFlow.residuals returns (no counterpart in the reference: its loss keeps these maps to itself)
 
 The reference's own dataclasses are accepted everywhere these are (duck typing): the
 drop-in never checks the class, only the attribute names.
@@ -65,3 +66,25 @@ class ModelOutput:
     intrinsics: Tensor  # (batch, frame, 3, 3)
     extrinsics: Tensor  # (batch, frame, 4, 4)
     backward_correspondence_weights: Tensor  # (batch, frame-1, H, W)
+
+
+@dataclass
+class FlowResiduals:
+    """The per-pixel terms of LossFlow.compute_unweighted_loss (flowmap/loss/loss_flow.py:46-68) for the pairs
+    [first_pair, first_pair + count) — LossFlow.residuals."""
+
+    forward: Tensor  # (batch, count, H, W): mapping.forward(xy_flowed_forward − xy, flows.forward, (H, W)), before the mask
+    backward: Tensor  # (batch, count, H, W)
+    forward_flow: Optional[Tensor]  # (batch, count, H, W, 2): xy_flowed_forward − xy, the pose-induced flow; None unless asked for
+    backward_flow: Optional[Tensor]
+    pair_sum: Optional[Tensor]  # (batch, count, 2) float64: Σ residual·mask per pair, [..., 0] forward, [..., 1] backward; None unless asked for
+    pair_valid: Optional[Tensor]  # (batch, count, 2) float64: Σ mask
+    first_pair: int
+
+    def pair_loss(self) -> Tensor:
+        """pair_sum / (pair_valid or 1): each pair's and direction's own masked mean."""
+        if self.pair_sum is None:
+            raise RuntimeError("flowmap_amd: FlowResiduals.pair_loss needs the sums (LossFlow.residuals(..., sums=True))")
+        from .loss.loss import or_one
+
+        return self.pair_sum / or_one(self.pair_valid)

@@ -41,8 +41,9 @@ extern "C" {
  * non-zero correction through a device flag; fm_track_presample and the `presampled` argument of fm_track_loss_fused_fwd_taps; round 6,
  * version 6: that entry point and that argument are gone again — measured, not adopted: docs/history/patches/r05_track_presample.patch; version 7: the bit-mask packed format of the fused flow
  * loss — fm_flow_masks_binary, fm_flow_pack_inputs_bitmask(_views), fm_flow_loss_fused_bitmask; the existing entries are unchanged; version 8: the regressed
- * extrinsics — fm_quat_pose_fwd / fm_quat_pose_bwd; the existing entries are unchanged).  A binding checks fm_abi_version() == FM_ABI_VERSION when it loads the library. */
-#define FM_ABI_VERSION 8
+ * extrinsics — fm_quat_pose_fwd / fm_quat_pose_bwd; the existing entries are unchanged; version 9: the flow residual maps —
+ * fm_flow_residuals / fm_flow_residual_blocks; the existing entries are unchanged).  A binding checks fm_abi_version() == FM_ABI_VERSION when it loads the library. */
+#define FM_ABI_VERSION 9
 int fm_abi_version(void);
 
 #define FM_STAT_STRIDE 16      /* doubles per pair in `stats` */
@@ -721,6 +722,37 @@ int fm_flow_loss_fused_bitmask(float* depth, const float* k, const float* kinv, 
 int fm_quat_pose_fwd(const float* quat, const float* trans, int pairs, float* t_bwd, float* t_fwd, float* ext, void* stream);
 int fm_quat_pose_bwd(const float* quat, const float* trans, const float* t_fwd, const float* g_t_bwd, const float* g_t_fwd,
                      const float* g_rel_chain, int pairs, float* g_quat, float* g_trans, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Flow residual maps (ABI version 9).  The per-pixel and per-pair quantities of LossFlow.compute_unweighted_loss
+ * (flowmap/loss/loss_flow.py:46-68) straight from depth, for a window of pairs, in ONE pass over depth: nothing of size
+ * (B,F,H,W,3) or a position tensor is formed.  The forward term of pair i reads frame i's depth, the backward term frame i+1's.
+ *
+ *   depth, k, kinv, t_fwd, t_bwd, flow_*, mask_*, batch .. aspect_y: as fm_flow_loss_fused takes them — the WHOLE stacks
+ *     (B,F,...) / (B,F-1,...); layouts[5] = depth, flow_fwd, flow_bwd, mask_fwd, mask_bwd (fm_layout) or NULL = all dense.
+ *     mask_fwd / mask_bwd may be NULL when no sums are asked for.
+ *   first_pair, count: the pairs [first_pair, first_pair + count) of every batch entry, 0 <= first_pair, count >= 1,
+ *     first_pair + count <= F - 1, B·count <= 65535.
+ *   residual_fwd, residual_bwd (B,count,H,W) out: mapping.forward(xy_flowed − xy, flow, (H,W)) BEFORE the mask — the arithmetic of
+ *     the fused pass (fm_math.h: flow_term_fast); a pixel whose Z'+1e-5 is not invertible, which the fused pass drops, gets the
+ *     reference's clamped value (project_camera_space: ±1e8, NaN -> 0).
+ *   pred_fwd, pred_bwd (B,count,H,W,2) out, or both NULL: xy_flowed − xy, the pose-induced flow.
+ *   pair_sum, pair_valid (B,count,2) doubles out, or both NULL: Σ (double)(residual·mask) and Σ (double)mask per pair and
+ *     direction ([..][0] forward, [..][1] backward), accumulated in fp64 from the pixel upward WITHOUT atomics: every workgroup
+ *     leaves its partial in `workspace` — (B,count,2,blocks,2) doubles, blocks from fm_flow_residual_blocks, contents
+ *     unspecified on entry and on return — and a second small launch adds a pair's partials in ascending workgroup order.  The
+ *     split of a pair into workgroups depends on (H, W) only: the sums are bit-reproducible, and bit-identical whether a pair is
+ *     reached through the full range or through a window.
+ * EVERY element of every output is written (no zero fill beforehand).  One thread per four adjacent pixels; 16-byte loads and
+ * stores when W % 4 == 0 and every base and stride is 16-byte aligned, else a scalar path with the same results.
+ *
+ * fm_flow_residual_blocks: blocks[0] (HOST int) = workgroups per (pair, direction) at this image size. */
+int fm_flow_residual_blocks(int height, int width, int* blocks);
+int fm_flow_residuals(const float* depth, const float* k, const float* kinv, const float* t_fwd, const float* t_bwd, const float* flow_fwd,
+                      const float* flow_bwd, const float* mask_fwd, const float* mask_bwd, int batch, int frames, int height, int width,
+                      int mapping_kind, float delta, float aspect_x, float aspect_y, int first_pair, int count, float* residual_fwd,
+                      float* residual_bwd, float* pred_fwd, float* pred_bwd, double* pair_sum, double* pair_valid, double* workspace,
+                      const fm_layout* layouts, void* stream);
 
 #ifdef __cplusplus
 }
