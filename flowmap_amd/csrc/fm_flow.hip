@@ -253,6 +253,66 @@ __device__ __forceinline__ void flow_term_pair(const DirPair& d, v2f arow, v2f b
   }
 }
 
+// ---------------------------------------------------------------------------------
+// The per-(frame, direction) constants, once per step.  make_dir has ONE result per (frame, direction) — 299 at C1 — and is ~90 fp64
+// instructions; in flow_fused_kernel's prologue every one of its 135 000 waves recomputed two of them on the unit that limits the
+// kernel (230 of a wave's ~2 700 VALU instructions).  flow_dir_table_kernel — one thread per (frame, direction), enqueued in front of
+// the fused kernel on the same stream — runs the very same loads and the same make_dir and leaves the 12 floats in the PADDING of the
+// `acc` entry they belong to: doubles kFlowAcc .. kFlowAcc+5 of its kFlowAccStride, which no sum uses, which flow_finalize_kernel
+// clears with the rest of the entry, and which belongs to the caller's workspace (per stream, no allocation here).  The fused kernel
+// reads them back through the constant address space: wave-uniform scalar loads into SGPRs, field by field.
+// -DFM_FLOW_CONSTS_IN_KERNEL keeps the prologue as it was, for A/B runs (tools/build_lib_variants.sh, tools/flow_microbench.py).
+// ---------------------------------------------------------------------------------
+constexpr int kDirConstFloats = 12;
+static_assert(sizeof(DirConst) == kDirConstFloats * sizeof(float), "DirConst is 12 floats");
+static_assert(kFlowAcc * sizeof(double) + sizeof(DirConst) <= kFlowAccStride * sizeof(double), "the constants fit in the padding of an acc entry");
+
+struct DirTableParams {
+  const float* k;      // (B,F,3,3)
+  const float* kinv;   // (B,F,3,3)
+  const float* t_fwd;  // (B,F-1,4,4)
+  const float* t_bwd;  // (B,F-1,4,4)
+  double* acc;         // (B*F, 2, kFlowAccStride)
+  int total, frames;   // total = B·F
+  float ax, ay;
+};
+
+// entry: the (frame, direction) entry of `acc`
+__device__ __forceinline__ void store_dir_const(double* entry, const DirConst& d) {
+  float* out = reinterpret_cast<float*>(entry + kFlowAcc);
+  out[0] = d.au, out[1] = d.a1, out[2] = d.a2, out[3] = d.ta;
+  out[4] = d.bu, out[5] = d.b1, out[6] = d.b2, out[7] = d.tb;
+  out[8] = d.cu, out[9] = d.c1, out[10] = d.c2, out[11] = d.tc;
+}
+
+__global__ void __launch_bounds__(64) flow_dir_table_kernel(DirTableParams p) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;  // (batch·frames + frame, direction)
+  if (i >= 2 * p.total) return;
+  const int bf = i >> 1;
+  const bool backward = (i & 1) != 0;
+  const int f = bf % p.frames, b = bf / p.frames;
+  if (backward ? f == 0 : f == p.frames - 1) return;  // the frame has no such neighbour: nothing reads this entry's padding
+  const size_t pair_f = (size_t)b * (p.frames - 1) + f;  // pair whose earlier frame is f
+  Mat3 kinv, kd;
+  Pose t;
+  load_mat3(p.kinv + (size_t)bf * 9, kinv);
+  load_mat3(p.k + (size_t)(backward ? bf - 1 : bf + 1) * 9, kd);
+  load_pose44(backward ? p.t_bwd + (pair_f - 1) * 16 : p.t_fwd + pair_f * 16, t);
+  DirConst d;
+  make_dir(t, kinv, kd, p.ax, p.ay, d);
+  store_dir_const(p.acc + (size_t)i * kFlowAccStride, d);
+}
+
+// entry: the (frame, direction) entry of `acc`.  Nothing writes the padding while the fused kernel runs (its atomics land on the first
+// kFlowAcc doubles), so the loads may be scalar ones: the constant address space says so to the compiler.
+__device__ __forceinline__ void load_dir_const(const double* entry, DirConst& d) {
+  typedef const __attribute__((address_space(4))) float* const_floats;
+  const const_floats t = (const_floats)(entry + kFlowAcc);
+  d.au = t[0], d.a1 = t[1], d.a2 = t[2], d.ta = t[3];
+  d.bu = t[4], d.b1 = t[5], d.b2 = t[6], d.tb = t[7];
+  d.cu = t[8], d.c1 = t[9], d.c2 = t[10], d.tc = t[11];
+}
+
 #ifndef FM_FLOW_WAVES
 // Waves per SIMD the register allocator must leave room for.  3 (<=168 VGPRs; the packed pair of terms uses 150, the scalar
 // form 106, no scratch).  Round 2's scalar kernel: 3 beat 4 by 3-5 % and 2 by 4 %; round 3 (tools/flow_microbench.py, tools/ab_flow.sh):
@@ -320,9 +380,18 @@ __global__ void __launch_bounds__(256, (PACKED == kFmtBits && !TAPS) ? FM_FLOW_W
   }
   __syncthreads();
 
+  DirConst df, db;
+#ifndef FM_FLOW_CONSTS_IN_KERNEL
+  {
+    // flow_dir_table_kernel left both directions' constants in the padding of this frame's `acc` entries.  (A direction the frame
+    // does not have was never written: the other one is read in its place, and zeroed in make_pair / skipped by the scalar form.)
+    const double* entry = p.acc + (size_t)bf * 2 * kFlowAccStride;
+    load_dir_const(entry + (has_fwd ? 0 : kFlowAccStride), df);
+    load_dir_const(entry + (has_bwd ? kFlowAccStride : 0), db);
+  }
+#else
   const size_t pair_f = (size_t)b * (p.frames - 1) + f;  // pair whose earlier frame is f
   const size_t pair_b = pair_f - 1;                       // pair whose later frame is f
-  DirConst df, db;
   {
     // (both directions unconditionally, on in-range stand-ins where the frame has no such neighbour — conditional initialisation
     // of the two structs costs a scratch allocation; the stand-in's constants are zeroed in make_pair)
@@ -336,6 +405,7 @@ __global__ void __launch_bounds__(256, (PACKED == kFmtBits && !TAPS) ? FM_FLOW_W
     load_pose44(p.t_bwd + (has_bwd ? pair_b : pair_f) * 16, t);
     make_dir(t, kinv, kd, p.ax, p.ay, db);
   }
+#endif
   const DirPair dp = make_pair(df, db, has_fwd ? 1.f : 0.f, has_bwd ? 1.f : 0.f);  // (a direction this frame does not have: zeros)
   const float scale = GRAD ? p.scale[0] : 0.f;
   const float inv_delta = KIND == kHuber ? 1.0f / p.delta : 0.f;
@@ -858,6 +928,12 @@ static int flow_loss_launch(const float* depth, const float* k, const float* kin
   } while (0)
   FM_CHECK_ARG(!adam || (vec == 4 && grad && grad_depth));
   FM_CHECK_ARG(!taps || vec == 4);
+#ifndef FM_FLOW_CONSTS_IN_KERNEL
+  {  // the (frame, direction) constants into the padding of `acc`, in front of the pass that reads them (same stream)
+    const DirTableParams tp{k, kinv, t_fwd, t_bwd, acc, batch * frames, frames, aspect_x, aspect_y};
+    hipLaunchKernelGGL(flow_dir_table_kernel, dim3((unsigned)((2 * batch * frames + 63) / 64)), dim3(64), 0, st, tp);
+  }
+#endif
   if (vec == 4) FM_FLOW_VEC(4);
 #ifdef FM_FLOW_FORCE_VEC2
   else if (vec == 2) FM_FLOW_KIND(2, kFmtNone);

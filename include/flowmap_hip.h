@@ -65,7 +65,12 @@ int fm_abi_version(void);
  *   grad_depth (B,F,H,W) out: dL/ddepth with poses held fixed (may be NULL).
  *   acc (B*F, 2, FM_FLOW_ACC_STRIDE) fp64 in/out: per (source frame, direction) sums are ADDED into it: it must
  *          be zero on entry.  fm_flow_loss_finalize consumes it and leaves it zero again, so a workspace kept
- *          across steps is zeroed once, when it is allocated.
+ *          across steps is zeroed once, when it is allocated.  Only the first 13 doubles of an entry are sums.  The rest of the
+ *          stride is SCRATCH between this call and fm_flow_loss_finalize: the call first enqueues a small kernel (one thread
+ *          per (frame, direction), same stream) that leaves the twelve fp32 constants the pass derives from K, K⁻¹ and the
+ *          pose of that direction in doubles 13..18 of the entry, and the pass reads them from there instead of recomputing
+ *          them in every wave; finalize clears them with the sums.  A caller that reads `acc` itself reads the first 13
+ *          doubles of an entry and nothing else; two calls in flight on two streams need two workspaces, as before.
  *   packed: NULL, or flows + masks re-laid-out by fm_flow_pack_inputs — then flow_* / mask_*
  *          are not read (may be NULL).  Same bytes, one stream instead of six (needs W % 4 == 0).
  *   items_per_thread: tuning knob (<=0 -> default).
