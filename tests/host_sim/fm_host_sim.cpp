@@ -1419,6 +1419,10 @@ int fm_track_loss_fused_fwd(const float* depth, int depth_frame0, int own_first,
                             const int32_t* tiles, int ntiles, int pmax, int fmax, int height, int width, int kind, float delta, float ax,
                             float ay, float weight, float* ws, uint8_t* flag, float* tgt, float* partial, double* acc, float* loss,
                             float* scale, double* totals, float* gws, double* acc2, void* stream) {
+  // (the library's argument checks: csrc/fm_track.hip)
+  if (!(depth && kinv && ext && ext_inv && k && xy && vis && seg && tiles && ws && flag && tgt && partial && acc && loss && scale)) return 1;
+  if (!(ntiles >= 1 && pmax >= 1 && fmax >= 1 && frames >= 1 && kind >= 0 && kind <= 2 && depth_frame0 >= 0)) return 1;
+  if (!((gws == nullptr) == (acc2 == nullptr) && own_first >= depth_frame0 && own_end >= own_first)) return 1;
   // the (segment, frame) entries of the listed tiles: owned ones are sampled, the others flagged invisible
   std::vector<int32_t> blocks;
   for (int tile = 0; tile < ntiles; ++tile) {
