@@ -118,6 +118,8 @@ SIGNATURES = {
     "fm_quat_pose_bwd": [P, P, P, P, P, P, I, P, P, P],
     "fm_flow_residual_blocks": [I, I, P],
     "fm_flow_residuals": [P] * 9 + [I, I, I, I, I, F, F, F, I, I] + [P] * 9,
+    "fm_track_residual_workspace": [I, I, P],
+    "fm_track_residuals": [P] * 5 + [I, P, P, P, I, I, I, I, I, I, I, F, F, F] + [P] * 10,
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -231,7 +231,7 @@ def _dense_flow_is_rough(bwd_flow: Tensor, h: int, w: int) -> bool:
 
 # which backward path the facades selected (tests)
 counters = {"procrustes_planned": 0, "procrustes_dense_planned": 0, "flow_packs": 0, "flow_packs_bitmask": 0, "procrustes_plans_built": 0, "track_tap_samples": 0,
-            "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0, "flow_residuals": 0}
+            "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0, "flow_residuals": 0, "track_residuals": 0}
 
 
 class LeadingFrames:
@@ -725,6 +725,31 @@ def flow_residuals(depth, k, t_fwd, t_bwd, flow_fwd, flow_bwd, mask_fwd, mask_bw
                                      int(count), bool(predicted_flow), bool(sums))
     counters["flow_residuals"] += 1
     return tuple(x if x.numel() else None for x in out)
+
+
+def track_residuals(depth, k, ext, packed, first, count, kind, delta, predicted, sums):
+    """The per-(source frame, target frame, point) tracking terms of the packed segments [first, first + count) straight from depth
+    (csrc/fm_torch.cpp: track_residuals_op -> fm_track_residuals): one tuple (residual (1,f,f,P), visible (1,f,f,P) bool, xy_target
+    (1,f,f,P,2), pair_sum (f,f), pair_count (f,f), track_sum (P,), track_count (P,)) per segment — views of the launch's flat outputs —
+    None for what was not asked for.  One launch, plus the small table of target constants before it and the ordered second stage of
+    the sums after it.  Reads its arguments and nothing else: no DepthSink, no tap plan or tap image, no optimiser ticket, no note on
+    any tensor beyond the cached K^-1 the fused loss keeps as well."""
+    if packed.partial or packed.counts[7] != 0 or packed.counts[8] >= 0:
+        raise RuntimeError("flowmap_amd: the tracking residuals take a track list packed for ALL source frames, not a frame shard's (PackedTracks(own=...))")
+    shapes = packed.shapes[first:first + count]
+    kinv = intrinsics_inverse(k)
+    flat = torch_ops().track_residuals(depth, k, kinv, ext, packed.xy, packed.vis, packed.seg, packed.counts, [f for f, _ in shapes], [p for _, p in shapes],
+                                       int(first), int(kind), float(delta), bool(predicted), bool(sums))
+    counters["track_residuals"] += 1
+    residual, visible, xy_target, pair_sum, pair_count, track_sum, track_count = flat
+    out, e, q, n = [], 0, 0, 0
+    for f, p in shapes:
+        m = f * f * p
+        out.append((residual[e:e + m].view(1, f, f, p), visible[e:e + m].view(1, f, f, p), xy_target[e:e + m].view(1, f, f, p, 2) if predicted else None,
+                    *((pair_sum[q:q + f * f].view(f, f), pair_count[q:q + f * f].view(f, f), track_sum[n:n + p], track_count[n:n + p]) if sums
+                      else (None, None, None, None))))
+        e, q, n = e + m, q + f * f, n + p
+    return out
 
 
 def softmin_intrinsics(depth, weights, bwd_flow, indices, candidate_k, rel, weight_sens, frames):

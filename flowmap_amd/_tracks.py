@@ -42,6 +42,7 @@ class PackedTracks:
             tiles.extend([s_idx, fr] for fr in range(0, f, TRACK_TILE) if any(owned(start + q) for q in range(fr, min(fr + TRACK_TILE, f))))
             offset += f * p
         self.total = offset
+        self.shapes = [(s_[1], s_[2]) for s_ in seg]  # (f, P) per segment: the host's copy of what `seg` holds on the device
         self.partial = own is not None  # some (segment, frame) entries are not sources here: flags start at 0
         self.xy = torch.cat(xy).contiguous()
         self.vis = torch.cat(vis).contiguous()

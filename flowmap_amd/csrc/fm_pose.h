@@ -587,6 +587,82 @@ FM_HD void track_pair_term(const float (&tg)[kTrackTgt], const float xw[3], floa
   a[13] += loc[13];
 }
 
+// One (source fs, target ft, point) element of LossTracking.residuals (fm_track_residuals.hip; the host build runs the same code): the
+// UNMASKED term ρ = mapping.forward(xy_target, xy[ft, p], (h, w)) (loss_tracking.py:48-56), the reprojected position and the in-frame bit
+// of the target (projection.py:291-296), by the forward half of track_pair_term_scaled — the same fma sequence, the same fm_rcp, the same
+// unsigned compares, the same Huber form — so the value is the hot path's own.  The fused pass gives a pair whose Z'+eps is not
+// invertible a zero weight; a map has to show it, so such an element takes the function-level route with the reference's clamp
+// semantics (project_point: ±1e8 / NaN -> 0, then K, then robust_map): finite for every mapping, and never in frame.
+// ext_inv44 / k33: inv(E_ft) and K_ft, read only on that route.
+// The source point of such an element, as track_sample (fm_track.hip) forms it: xyz = Σ_taps w_k · (K⁻¹[u_k, v_k, 1] · z_k) from the
+// four border-clamped taps of the source frame's DEPTH image, then X_w = E_fs · [xyz; 1].
+FM_HD void track_source_point(const float* depth_frame, const float* kinv9, const float* ext44, float x01, float y01, int height, int width,
+                              float xw[3]) {
+  Mat3 ki;
+  Pose e;
+  load_mat3(kinv9, ki);
+  load_pose44(ext44, e);
+  const Taps t = bilinear_taps(x01, y01, height, width);
+  float xyz[3] = {0.f, 0.f, 0.f};
+  for (int k = 0; k < 4; ++k) {
+    if (!t.in[k]) continue;
+    const int tc = tap_col(t, k), tr = tap_row(t, k);
+    float ray[3];
+    ray_dir(ki, pixel_center(tc, width), pixel_center(tr, height), ray);
+    const float z = depth_frame[(size_t)tr * width + tc];
+    xyz[0] += (ray[0] * z) * t.w[k];
+    xyz[1] += (ray[1] * z) * t.w[k];
+    xyz[2] += (ray[2] * z) * t.w[k];
+  }
+  apply_pose(e, xyz, xw);
+}
+
+struct TrackResidual {
+  float rho;   // before visibility
+  float u, v;  // xy_target
+  bool inside;
+};
+
+template <int KIND>
+FM_HD TrackResidual track_residual_at(const float (&ts)[kTrackTgt], const float xw[3], float gt_xs, float gt_ys, float delta, float inv_delta,
+                                      float ax, float ay, const float* ext_inv44, const float* k33) {
+  const float xu = fmaf(ts[0], xw[0], fmaf(ts[1], xw[1], fmaf(ts[2], xw[2], ts[3])));
+  const float xv = fmaf(ts[4], xw[0], fmaf(ts[5], xw[1], fmaf(ts[6], xw[2], ts[7])));
+  const float x2 = fmaf(ts[8], xw[0], fmaf(ts[9], xw[1], fmaf(ts[10], xw[2], ts[11])));
+  const float q = fm_rcp(x2 + kProjEps);
+  TrackResidual o;
+  if (fabsf(q) <= 3.0e38f) {
+    const float u = fmaf(xu, q, 0.f), v = fmaf(xv, q, 0.f);  // ax·u, ay·v; (−0) + (+0) = +0
+    o.inside = track_float_bits(u) < track_float_bits(ax) && track_float_bits(v) < track_float_bits(ay);
+    const float rx = u - gt_xs, ry = v - gt_ys;
+    const float ss = fmaf(rx, rx, ry * ry);
+    if (KIND == kL2) {
+      o.rho = 0.5f * ss;
+    } else if (KIND == kL1) {
+      o.rho = ss * (ss > 0.f ? fm_rsq(ss) : 0.f);
+    } else {
+      const float t = ss * fminf(fm_rsq(ss), inv_delta);
+      o.rho = fmaf(-0.5f, fminf(t, delta), t);
+    }
+    o.u = u / ax;
+    o.v = v / ay;
+    return o;
+  }
+  Pose einv;
+  Mat3 k;
+  load_pose44(ext_inv44, einv);
+  load_mat3(k33, k);
+  float xc[3];
+  apply_pose(einv, xw, xc);
+  const Projected pr = project_point(xc, k);
+  o.u = pr.u;
+  o.v = pr.v;
+  o.inside = false;
+  float dx, dy;
+  o.rho = robust_map(KIND, delta, pr.u * ax - gt_xs, pr.v * ay - gt_ys, dx, dy);
+  return o;
+}
+
 // Source-role step of one point once its dL/dX_w is complete: b[21] = this point's terms of
 // acc2, gxyz = dL/dxyz = R_fsᵀ · gX_w (scattered into dL/ddepth by fm_track_scatter).
 FM_HD void track_source_term(const Pose& e_s, const float* ws9, const float gxw[3], float (&b)[21], float gxyz[3]) {
@@ -629,3 +705,9 @@ FM_HD void track_frame_grads(const double* a, const double* b, double sc, const 
 }
 
 }  // namespace fm
+
+// (a host build's serial entry points of the tracking residual maps; fm_math.h, which includes the other host headers, comes BEFORE the
+// functions of this file they need)
+#if !defined(__HIPCC__)
+#include "fm_track_residuals_host.h"
+#endif

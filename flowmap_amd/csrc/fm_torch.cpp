@@ -50,7 +50,7 @@ using OptTensor = std::optional<Tensor>;
   X(fm_depth_gather) X(fm_extrinsics_inverse) X(fm_track_loss_fused_fwd) X(fm_track_loss_bwd) X(fm_adam_step)                 \
   X(fm_adam_step_capturable) X(fm_softmin_score_fwd) X(fm_softmin_score_bwd) X(fm_softmin_blend_fwd) X(fm_softmin_blend_bwd)         \
   X(fm_random_subset) X(fm_random_subset_stateful) X(fm_abi_version) X(fm_flow_loss_fused_taps) X(fm_track_loss_fused_fwd_taps) X(fm_tap_grad_apply) \
-  X(fm_flow_loss_fused_bitmask) X(fm_flow_residuals) X(fm_flow_residual_blocks)
+  X(fm_flow_loss_fused_bitmask) X(fm_flow_residuals) X(fm_flow_residual_blocks) X(fm_track_residuals) X(fm_track_residual_workspace)
 
 struct Api {
 #define X(name) decltype(&::name) name = nullptr;
@@ -1567,6 +1567,67 @@ static std::vector<Tensor> flow_residuals_op(const Tensor& depth_in, const Tenso
   return {res_f, res_b, pred_f, pred_b, pair_sum, pair_valid};
 }
 
+// LossTracking.residuals on lazy surfaces (fm_track_residuals): residual, visibility, optionally the reprojected positions and the
+// per-pair / per-track masked sums of the packed segments [first, first + seg_frames.size()), straight from depth.  seg_frames /
+// seg_points: f and P of those segments (the host's copy of what `seg` holds on the device).  Not differentiable.  -> {residual,
+// visible, xy_target, pair_sum, pair_count, track_sum, track_count}, every one FLAT, the segments' shares one after the other
+// ([fs][ft][p], [fs][ft], [p]); what was not asked for comes back as an empty tensor.
+static std::vector<Tensor> track_residuals_op(const Tensor& depth_in, const Tensor& k_in, const Tensor& kinv_in, const Tensor& ext_in, const Tensor& xy,
+                                              const Tensor& vis, const Tensor& seg, std::vector<int64_t> counts, std::vector<int64_t> seg_frames,
+                                              std::vector<int64_t> seg_points, int64_t first, int64_t kind, double delta, bool predicted, bool sums) {
+  at::NoGradGuard no_grad;
+  const auto dev = check_device({&depth_in, &k_in, &kinv_in, &ext_in, &xy, &vis, &seg});
+  const Tensor depth = f32c(depth_in.detach(), "depth"), k = f32c(k_in.detach(), "intrinsics"), kinv = f32c(kinv_in.detach(), "inverse intrinsics"),
+               ext = f32c(ext_in.detach(), "extrinsics");
+  TORCH_CHECK(counts.size() == 9, "flowmap_amd: packed track counts");
+  TORCH_CHECK(depth.dim() == 4 && depth.size(0) == 1, "flowmap_amd: the tracking residuals support batch size 1 (as the reference asserts)");
+  TORCH_CHECK(ext.dim() == 4 && ext.size(0) == 1 && ext.size(2) == 4 && ext.size(3) == 4, "flowmap_amd: extrinsics must be (1, frame, 4, 4)");
+  const int64_t f = ext.size(1), h = depth.size(2), w = depth.size(3), total = counts[4], count = (int64_t)seg_frames.size();
+  TORCH_CHECK(depth.size(1) == f, "flowmap_amd: the tracking residuals need every frame's depth (depth holds ", depth.size(1), " of ", f,
+              " frames: a frame shard)");
+  TORCH_CHECK(counts[5] == 0 && counts[7] == 0 && counts[8] < 0, "flowmap_amd: the tracking residuals take a track list packed for ALL source frames, not a frame shard's");
+  TORCH_CHECK(k.sizes() == at::IntArrayRef({1, f, 3, 3}) && kinv.sizes() == k.sizes(), "flowmap_amd: intrinsics shape does not match the extrinsics");
+  TORCH_CHECK(counts[6] <= f, "flowmap_amd: a track segment extends past the last frame");
+  TORCH_CHECK(h * w < (int64_t(1) << 30), "flowmap_amd: the tracking residuals index pixels inside a frame with 32 bits");
+  TORCH_CHECK(xy.scalar_type() == at::kFloat && xy.is_contiguous() && xy.numel() == total * 2 && vis.scalar_type() == at::kByte && vis.is_contiguous() &&
+                  vis.numel() == total && seg.scalar_type() == at::kInt && seg.is_contiguous() && seg.dim() == 2 && seg.size(1) == 4,
+              "flowmap_amd: packed tracks: xy (total, 2) float32, vis (total) uint8, seg (S, 4) int32");
+  TORCH_CHECK(count >= 1 && seg_points.size() == seg_frames.size() && first >= 0 && first + count <= seg.size(0), "flowmap_amd: the segment window [", first,
+              ", ", first + count, ") does not lie in the ", seg.size(0), " segments");
+  int64_t elems = 0, pairs = 0, points = 0, work_doubles = 0, fmax = 1, pmax = 1;
+  for (int64_t i = 0; i < count; ++i) {
+    const int64_t sf = seg_frames[i], sp = seg_points[i];
+    TORCH_CHECK(sf >= 1 && sp >= 1 && sf <= f && sp <= total, "flowmap_amd: a segment of ", sf, " frames and ", sp, " points");
+    elems += sf * sf * sp;
+    pairs += sf * sf;
+    points += sp;
+    fmax = std::max(fmax, sf);
+    pmax = std::max(pmax, sp);
+    if (sums) {
+      long one = 0;
+      FM_CALL(fm_track_residual_workspace, (int)sf, (int)sp, &one);
+      work_doubles += one;
+    }
+  }
+  const auto fopt = depth.options();
+  Tensor ext_inv = at::empty_like(ext), tgt = at::empty({f, 12}, fopt);
+  Tensor residual = at::empty({elems}, fopt), visible = at::empty({elems}, fopt.dtype(at::kBool));
+  Tensor xy_target = predicted ? at::empty({elems, 2}, fopt) : at::empty({0}, fopt);
+  const auto dopt = fopt.dtype(at::kDouble);
+  Tensor pair_sum = at::empty({sums ? pairs : 0}, dopt), pair_count = at::empty({sums ? pairs : 0}, dopt);
+  Tensor track_sum = at::empty({sums ? points : 0}, dopt), track_count = at::empty({sums ? points : 0}, dopt), work;
+  if (sums) work = at::empty({work_doubles}, dopt);
+  const float sc = std::sqrt((float)(h * w));
+  DeviceScope scope(dev);
+  FM_CALL(fm_extrinsics_inverse, ptr(ext), (int)f, ptr(ext_inv), scope.stream);
+  FM_CALL(fm_track_residuals, ptr(depth), ptr(kinv), ptr(ext), ptr(ext_inv), ptr(k), (int)f, ptr(xy), ptr<uint8_t>(vis), ptr<int32_t>(seg), (int)first,
+          (int)count, (int)pmax, (int)fmax, (int)h, (int)w, (int)kind, (float)delta, (float)w / sc, (float)h / sc, ptr(tgt), ptr(residual),
+          static_cast<uint8_t*>(visible.data_ptr()), predicted ? ptr(xy_target) : nullptr, sums ? ptr<double>(pair_sum) : nullptr,
+          sums ? ptr<double>(pair_count) : nullptr, sums ? ptr<double>(track_sum) : nullptr, sums ? ptr<double>(track_count) : nullptr,
+          sums ? ptr<double>(work) : nullptr, scope.stream);
+  return {residual, visible, xy_target, pair_sum, pair_count, track_sum, track_count};
+}
+
 }  // namespace fmt
 
 TORCH_LIBRARY(flowmap_amd, m) {
@@ -1645,4 +1706,7 @@ TORCH_LIBRARY(flowmap_amd, m) {
   m.def("flow_residuals(Tensor depth, Tensor k, Tensor kinv, Tensor t_fwd, Tensor t_bwd, Tensor flow_fwd, Tensor flow_bwd, Tensor mask_fwd, Tensor mask_bwd, "
         "int kind, float delta, int first_pair, int count, bool predicted_flow, bool sums) -> Tensor[]",
         fmt::flow_residuals_op);
+  m.def("track_residuals(Tensor depth, Tensor k, Tensor kinv, Tensor ext, Tensor xy, Tensor vis, Tensor seg, int[] counts, int[] seg_frames, int[] seg_points, "
+        "int first, int kind, float delta, bool predicted, bool sums) -> Tensor[]",
+        fmt::track_residuals_op);
 }

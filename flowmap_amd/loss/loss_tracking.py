@@ -10,7 +10,8 @@ from torch import Tensor
 
 import torch
 
-from .. import _ops
+from .. import _ops, _reference
+from ..types import TrackResiduals
 from ..model.projection import LazySurfaces, _dense_extrinsics, compute_track_flow
 from .loss import Loss, LossCfgCommon, or_one
 from .mapping import MappingCfg, get_mapping
@@ -104,3 +105,78 @@ class LossTracking(Loss[LossTrackingCfg]):
             counts.append(visible.sum())
         # ONE ratio over all segments (loss_tracking.py:58-61), `or 1` evaluated on the device
         return torch.stack(numerators).sum() / or_one(torch.stack(counts).sum())
+
+    # -- per-track view ---------------------------------------------------------------------
+    @staticmethod
+    def _segment_window(segments, total: int):
+        """``segments`` of residuals() -> (first, count): None (all segments), an int, a slice with step 1, or (first, count)."""
+        if segments is None:
+            first, count = 0, total
+        elif isinstance(segments, int) and not isinstance(segments, bool):
+            first, count = (segments + total if segments < 0 else segments), 1
+        elif isinstance(segments, slice):
+            if segments.step not in (None, 1):
+                raise ValueError(f"flowmap_amd: LossTracking.residuals takes a slice of segments with step 1 (got step {segments.step})")
+            first, stop, _ = segments.indices(total)
+            count = stop - first
+        elif isinstance(segments, (tuple, list)) and len(segments) == 2 and all(isinstance(x, int) and not isinstance(x, bool) for x in segments):
+            first, count = segments
+        else:
+            raise ValueError(f"flowmap_amd: LossTracking.residuals: segments must be None, an int, a slice with step 1 or (first, count), got {segments!r}")
+        if first < 0 or count < 1 or first + count > total:
+            raise ValueError(f"flowmap_amd: LossTracking.residuals: the segments [{first}, {first + count}) do not lie in the {total} segments of the track list")
+        return int(first), int(count)
+
+    def residuals(self, batch, tracks, model_output, segments=None, predicted: bool = False, sums: bool = True) -> list:
+        """The per-(source frame, target frame, point) quantities of ``compute_unweighted_loss`` (loss_tracking.py:44-61) for the segments
+        ``segments`` of ``tracks`` — None (all), an int, a slice with step 1, or (first, count): one ``TrackResiduals`` per segment, in list
+        order.  ``residual`` = mapping.forward(xy_target, segment.xy[:, None], (h, w)) BEFORE visibility, defined for every (fs, ft, p) as the
+        reference defines it (a source position outside [0,1)² samples the border-clamped surface); ``visible`` = the visibility
+        compute_track_flow returns; with ``predicted`` the reprojected positions ``xy_target``; with ``sums`` Σ residual where visible and
+        Σ visible per (fs, ft) and per track, in float64.
+
+        Output size: f·f·P·5 bytes per segment, f·f·P·13 with ``predicted`` — 10 and 27 MB for a segment of 41 frames and 35×35 points,
+        which is what the window argument is for.
+
+        On the model's own lazy surfaces (the fused loss's condition) all selected segments are ONE launch over depth (fm_track_residuals,
+        plus the small ordered second stage of the sums) and nothing of size (b,f,h,w,3) exists; with an explicit surfaces tensor it composes
+        compute_track_flow and the mapping; host tensors after install() go to the reference's own functions.  Never differentiable, and
+        it leaves the training step alone: no look-ahead or fused-Adam state, no tap plan or tap image, no announcement of track pixels."""
+        if tracks is None or len(tracks) == 0:
+            raise ValueError("flowmap_amd: LossTracking.residuals: there are no tracks (tracks is None or an empty list)")
+        first, count = self._segment_window(segments, len(tracks))
+        with torch.no_grad():
+            if self._fusable(model_output, tracks) and not _reference.on_host(batch):
+                return self._residuals_fused(tracks, model_output, first, count, predicted, sums)
+            return self._residuals_general(batch, tracks, model_output, first, count, predicted, sums)
+
+    def _residuals_fused(self, tracks, model_output, first: int, count: int, predicted: bool, sums: bool) -> list:
+        s: LazySurfaces = model_output.surfaces
+        ext = _dense_extrinsics(model_output.extrinsics).detach()
+        if s.depths.shape[1] != ext.shape[1]:
+            raise RuntimeError(f"flowmap_amd: LossTracking.residuals needs every frame's depth on this device (depth holds {s.depths.shape[1]} of "
+                               f"{ext.shape[1]} frames: a frame shard)")
+        packed = _ops.pack_tracks(tracks, s.depths.device)
+        out = _ops.track_residuals(s.depths.detach(), model_output.intrinsics.detach(), ext, packed, first, count, _ops.MAPPING_KINDS[self.mapping.kind],
+                                   self.mapping.delta, predicted, sums)
+        return [TrackResiduals(*fields, first + i, int(tracks[first + i].start_frame)) for i, fields in enumerate(out)]
+
+    def _residuals_general(self, batch, tracks, model_output, first: int, count: int, predicted: bool, sums: bool) -> list:
+        # host tensors after install(): the reference's own function (flowmap_amd/_reference.py); without install() ours refuses them
+        track_flow = _reference.host_twin("compute_track_flow", batch) or compute_track_flow
+        image_shape = tuple(batch.videos.shape[-2:])
+        out = []
+        for index in range(first, first + count):
+            segment = tracks[index]
+            if segment.xy.shape[0] != 1:
+                raise RuntimeError("flowmap_amd: LossTracking.residuals supports batch size 1 (as the reference asserts)")
+            window = slice(segment.start_frame, segment.start_frame + segment.xy.shape[1])
+            xy_target, visible = track_flow(model_output.surfaces[:, window], model_output.extrinsics[:, window], model_output.intrinsics[:, window], segment)
+            residual = self.mapping.forward(xy_target, segment.xy[:, None], image_shape)
+            fields = (None, None, None, None)
+            if sums:
+                shown = torch.where(visible, residual.to(torch.float64), torch.zeros((), dtype=torch.float64, device=residual.device))[0]
+                seen = visible.to(torch.float64)[0]
+                fields = (shown.sum(dim=2), seen.sum(dim=2), shown.sum(dim=(0, 1)), seen.sum(dim=(0, 1)))
+            out.append(TrackResiduals(residual.detach(), visible, xy_target.detach() if predicted else None, *fields, index, int(segment.start_frame)))
+        return out

@@ -6,6 +6,7 @@
   ModelOutput  flowmap/model/model.py:24-30
   BackboneOutput  flowmap/model/backbone/backbone.py:14-17
   FlowResiduals  what LossFlow.residuals returns (no counterpart in the reference: its loss keeps these maps to itself)
+  TrackResiduals  what LossTracking.residuals returns, one per segment (likewise)
 
 The reference's own dataclasses are accepted everywhere these are (duck typing): the
 drop-in never checks the class, only the attribute names.
@@ -88,3 +89,34 @@ class FlowResiduals:
         from .loss.loss import or_one
 
         return self.pair_sum / or_one(self.pair_valid)
+
+
+@dataclass
+class TrackResiduals:
+    """The per-(source frame, target frame, point) terms of LossTracking.compute_unweighted_loss (flowmap/loss/loss_tracking.py:44-61)
+    for ONE track segment of f frames and P points — LossTracking.residuals."""
+
+    residual: Tensor  # (1, f, f, P): mapping.forward(xy_target, segment.xy[:, None], (H, W)), BEFORE visibility; [0, fs, ft, p]
+    visible: Tensor  # (1, f, f, P) bool: the visibility compute_track_flow returns (projection.py:291-296)
+    xy_target: Optional[Tensor]  # (1, f, f, P, 2): the reprojected positions; None unless asked for
+    pair_sum: Optional[Tensor]  # (f, f) float64: Σ_p residual where visible; None unless asked for (as the three below)
+    pair_count: Optional[Tensor]  # (f, f) float64: Σ_p visible
+    track_sum: Optional[Tensor]  # (P,) float64: Σ_{fs,ft} residual where visible
+    track_count: Optional[Tensor]  # (P,) float64: Σ_{fs,ft} visible
+    segment: int  # index into the track list
+    start_frame: int
+
+    def _ratio(self, total, count, what: str) -> Tensor:
+        if total is None:
+            raise RuntimeError(f"flowmap_amd: TrackResiduals.{what} needs the sums (LossTracking.residuals(..., sums=True))")
+        from .loss.loss import or_one
+
+        return total / or_one(count)
+
+    def pair_loss(self) -> Tensor:
+        """pair_sum / (pair_count or 1): each (source frame, target frame)'s own masked mean."""
+        return self._ratio(self.pair_sum, self.pair_count, "pair_loss")
+
+    def track_loss(self) -> Tensor:
+        """track_sum / (track_count or 1): each track's own masked mean over all frame pairs."""
+        return self._ratio(self.track_sum, self.track_count, "track_loss")

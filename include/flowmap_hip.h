@@ -42,8 +42,9 @@ extern "C" {
  * version 6: that entry point and that argument are gone again — measured, not adopted: docs/history/patches/r05_track_presample.patch; version 7: the bit-mask packed format of the fused flow
  * loss — fm_flow_masks_binary, fm_flow_pack_inputs_bitmask(_views), fm_flow_loss_fused_bitmask; the existing entries are unchanged; version 8: the regressed
  * extrinsics — fm_quat_pose_fwd / fm_quat_pose_bwd; the existing entries are unchanged; version 9: the flow residual maps —
- * fm_flow_residuals / fm_flow_residual_blocks; the existing entries are unchanged).  A binding checks fm_abi_version() == FM_ABI_VERSION when it loads the library. */
-#define FM_ABI_VERSION 9
+ * fm_flow_residuals / fm_flow_residual_blocks; the existing entries are unchanged; version 10: the tracking residual maps —
+ * fm_track_residuals / fm_track_residual_workspace; the existing entries are unchanged).  A binding checks fm_abi_version() == FM_ABI_VERSION when it loads the library. */
+#define FM_ABI_VERSION 10
 int fm_abi_version(void);
 
 #define FM_STAT_STRIDE 16      /* doubles per pair in `stats` */
@@ -758,6 +759,36 @@ int fm_flow_residuals(const float* depth, const float* k, const float* kinv, con
                       int mapping_kind, float delta, float aspect_x, float aspect_y, int first_pair, int count, float* residual_fwd,
                       float* residual_bwd, float* pred_fwd, float* pred_bwd, double* pair_sum, double* pair_valid, double* workspace,
                       const fm_layout* layouts, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Tracking residual maps (ABI version 10).  The per-(source frame, target frame, point) quantities inside
+ * LossTracking.compute_unweighted_loss (flowmap/loss/loss_tracking.py:44-61) straight from depth, for a WINDOW of the packed
+ * segments, in one pass: no (F,H,W,3) surfaces, no position tensor per launch chain.  Batch 1, all frames local.
+ *
+ *   depth (F,H,W) dense; kinv, k (F,3,3); ext, ext_inv (F,4,4) (fm_extrinsics_inverse); xy (total,2), vis (total), seg (S,4) =
+ *     start_frame, f, p, offset: the packed track list as fm_track_loss_fused_fwd takes it — the WHOLE list; every segment must lie
+ *     inside the F frames.  pmax, fmax: at least the largest p and f of the window's segments.
+ *   first_segment, count: the segments [first_segment, first_segment + count) of seg.  Their shares of every output lie one after
+ *     the other in that order, segment s taking f_s·f_s·p_s elements ([fs][ft][p]), f_s·f_s pairs ([fs][ft]) and p_s points.
+ *   tgt (F,12) floats: scratch (the scaled target constants of every frame).
+ *   residual out: mapping.forward(xy_target, xy[ft, p], (H,W)) BEFORE visibility — the forward half of the fused pass's pair term
+ *     (fm_pose.h: track_residual_at); an element whose Z'+1e-5 is not invertible gets the reference's clamped value (±1e8, NaN -> 0).
+ *   visible out (bytes 0/1): vis[fs,p] ∧ vis[ft,p] ∧ xy[fs,p] ∈ [0,1)² ∧ xy_target ∈ [0,1)² (projection.py:291-296).
+ *   xy_target out (elements x 2 floats) or NULL: the reprojected positions.
+ *   pair_sum, pair_count (pairs), track_sum, track_count (points) doubles out, or all four NULL: Σ_p and Σ_{fs,ft} of
+ *     `visible ? (double)residual : 0` and of visible, WITHOUT atomics: a wave leaves its 64-point partial of a pair, a thread its
+ *     point's partial of a source frame, in `workspace` — Σ_s fm_track_residual_workspace(f_s, p_s) doubles over the window, 16-byte
+ *     aligned, contents unspecified on entry and on return — and a second launch adds them in ascending order.  The split depends on
+ *     the segment alone: the sums are bit-reproducible, and bit-identical whether a segment is reached through the full list or a window.
+ * EVERY element of every output is written.
+ *
+ * fm_track_residual_workspace: doubles[0] (HOST long) = workspace doubles of ONE segment of `frames` frames and `points` points. */
+int fm_track_residual_workspace(int frames, int points, long* doubles);
+int fm_track_residuals(const float* depth, const float* kinv, const float* ext, const float* ext_inv, const float* k, int frames, const float* xy,
+                       const uint8_t* vis, const int32_t* seg, int first_segment, int count, int pmax, int fmax, int height, int width,
+                       int mapping_kind, float delta, float aspect_x, float aspect_y, float* tgt, float* residual, uint8_t* visible,
+                       float* xy_target, double* pair_sum, double* pair_count, double* track_sum, double* track_count, double* workspace,
+                       void* stream);
 
 #ifdef __cplusplus
 }
