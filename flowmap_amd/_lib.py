@@ -120,6 +120,8 @@ SIGNATURES = {
     "fm_flow_residuals": [P] * 9 + [I, I, I, I, I, F, F, F, I, I] + [P] * 9,
     "fm_track_residual_workspace": [I, I, P],
     "fm_track_residuals": [P] * 5 + [I, P, P, P, I, I, I, I, I, I, I, F, F, F] + [P] * 10,
+    "fm_alignment_residual_workspace": [L, P],
+    "fm_alignment_residuals": [P] * 5 + [F, P, P, L, I, I, I, I, I, I] + [P] * 7,
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -58,6 +58,16 @@ def intrinsics_inverse(k: Tensor) -> Tensor:
     return kinv
 
 
+def intrinsics_inverse_peek(k: Tensor) -> Tensor:
+    """K^-1 for a read-only caller: what ``intrinsics_inverse`` left on K when it is there, else computed and NOT kept."""
+    k = _f32c(k, "intrinsics")
+    root = k if k._base is None else k._base
+    hit = root.__dict__.get("_fm_kinv", {}).get((k.data_ptr(), k.numel()))
+    if hit is not None and hit[0] == k._version:
+        return hit[1].view(k.shape)
+    return torch_ops().intrinsics_inverse(k)
+
+
 def _attach_inverse(k: Tensor, kinv: Tensor) -> None:
     k.__dict__.setdefault("_fm_kinv", {})[(k.data_ptr(), k.numel())] = (k._version, kinv)
 
@@ -231,7 +241,7 @@ def _dense_flow_is_rough(bwd_flow: Tensor, h: int, w: int) -> bool:
 
 # which backward path the facades selected (tests)
 counters = {"procrustes_planned": 0, "procrustes_dense_planned": 0, "flow_packs": 0, "flow_packs_bitmask": 0, "procrustes_plans_built": 0, "track_tap_samples": 0,
-            "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0, "flow_residuals": 0, "track_residuals": 0}
+            "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0, "flow_residuals": 0, "track_residuals": 0, "alignment_residuals": 0}
 
 
 class LeadingFrames:
@@ -750,6 +760,67 @@ def track_residuals(depth, k, ext, packed, first, count, kind, delta, predicted,
                       else (None, None, None, None))))
         e, q, n = e + m, q + f * f, n + p
     return out
+
+
+def alignment_residuals(depth, kinv, surfaces, bwd_flow, weights, weight_sens, rel, indices, first_pair, count, offsets, weight_map, sums):
+    """The terms of the Procrustes fit's objective for the pairs [first_pair, first_pair + count) (fm_alignment_residuals): (residual,
+    offset, weight, pair_sum, pair_weight), None for what was not asked for, shaped (b, count, P[, 3]) and (b, count).  ``depth`` +
+    ``kinv`` (depth-sourced) or ``surfaces`` (surface-sourced); ``weights`` a tensor, logits with ``weight_sens`` != 0, or None (weight 1);
+    ``rel`` (b, f-1, 4, 4) camera i+1 -> camera i; ``indices`` int64 or None (every pixel).  One launch, plus the ordered second stage of
+    the sums.  Reads its arguments and nothing else: no DepthSink, no tap plan, no arena, no note on any tensor."""
+    src = depth if depth is not None else surfaces
+    dev = check_device(src, kinv, bwd_flow, weights, rel, indices)
+    if depth is not None:
+        depth, kinv = _f32c(depth, "depth"), _f32c(kinv, "inverse intrinsics")
+        if depth.dim() != 4:
+            raise RuntimeError("flowmap_amd: depth must be (batch, frame, height, width)")
+        b, f, h, w = depth.shape
+        if tuple(kinv.shape) != (b, f, 3, 3):
+            raise RuntimeError(f"flowmap_amd: intrinsics shape {tuple(kinv.shape)} does not match depth {tuple(depth.shape)}")
+    else:
+        surfaces = _f32c(surfaces, "surfaces")
+        if surfaces.dim() != 5 or surfaces.shape[-1] != 3:
+            raise RuntimeError("flowmap_amd: surfaces must be (batch, frame, height, width, 3)")
+        b, f, h, w, _ = surfaces.shape
+    bwd_flow, rel = _f32c(bwd_flow, "backward flow"), _f32c(rel, "relative poses")
+    if tuple(bwd_flow.shape) != (b, f - 1, h, w, 2):
+        raise RuntimeError(f"flowmap_amd: flow shape {tuple(bwd_flow.shape)} does not match depth {(b, f, h, w)}")
+    if weights is not None:
+        weights = _f32c(weights, "correspondence weights")
+        if tuple(weights.shape) != (b, f - 1, h, w):
+            raise RuntimeError(f"flowmap_amd: weight shape {tuple(weights.shape)} does not match depth {(b, f, h, w)}")
+    if tuple(rel.shape) != (b, f - 1, 4, 4):
+        raise RuntimeError(f"flowmap_amd: pose shape {tuple(rel.shape)} does not match depth {(b, f, h, w)}")
+    if h * w >= 1 << 30:
+        raise RuntimeError(f"flowmap_amd: the alignment residuals index pixels inside a frame with 32 bits: height x width = {h * w} must stay below 2^30")
+    if first_pair < 0 or count < 1 or first_pair + count > f - 1:
+        raise RuntimeError(f"flowmap_amd: the pair window [{first_pair}, {first_pair + count}) does not lie in the {f - 1} pairs")
+    if b * count > 65535:
+        raise RuntimeError(f"flowmap_amd: the alignment residuals handle at most 65 535 pairs per call (batch x pairs = {b * count}): split the window")
+    if indices is not None:
+        indices = indices.contiguous()
+        points, maps = indices.numel(), (b, count, indices.numel())
+        if not 1 <= points < 1 << 30:
+            raise RuntimeError(f"flowmap_amd: the alignment residuals take between 1 and 2^30 - 1 indices (got {points})")
+    else:
+        points, maps = h * w, (b, count, h, w)
+    f32 = dict(dtype=torch.float32, device=dev)
+    residual = torch.empty(maps, **f32)
+    offset = torch.empty((*maps, 3), **f32) if offsets else None
+    weight = torch.empty(maps, **f32) if weight_map else None
+    pair_sum = pair_weight = work = None
+    if sums:
+        doubles = ctypes.c_long(0)
+        call("fm_alignment_residual_workspace", points, ctypes.byref(doubles))
+        pair_sum = torch.empty((b, count), dtype=torch.float64, device=dev)
+        pair_weight = torch.empty((b, count), dtype=torch.float64, device=dev)
+        work = torch.empty((b * count * doubles.value,), dtype=torch.float64, device=dev)
+    with _guard(dev):
+        call("fm_alignment_residuals", ptr(depth), ptr(kinv) if depth is not None else None, ptr(surfaces) if depth is None else None, ptr(bwd_flow),
+             ptr(weights), float(weight_sens) if weights is not None else 0.0, ptr(rel), ptr(indices), points, b, f, h, w, int(first_pair), int(count),
+             ptr(residual), ptr(offset), ptr(weight), ptr(pair_sum), ptr(pair_weight), ptr(work), stream_for(src))
+    counters["alignment_residuals"] += 1
+    return residual, offset, weight, pair_sum, pair_weight
 
 
 def softmin_intrinsics(depth, weights, bwd_flow, indices, candidate_k, rel, weight_sens, frames):

@@ -785,6 +785,18 @@ FM_HD Corr corr_load(const CorrSrc& s, const Mat3& kinv_e, const Mat3& kinv_l, i
   });
 }
 
+// The term of the fit's objective for one correspondence (align_rigid, procrustes.py:7-51, minimises Σ w‖T·p − q‖²): the offset
+// d = T·[p; 1] − q in the earlier camera's space, one fused multiply-add chain per component that starts from the translation (as
+// dense_bwd_t chains its products), and ‖d‖².  Explicit fmaf: the device kernel and the host build round alike.
+FM_HD float alignment_offset(const Pose& t, const float p[3], const float q[3], float d[3]) {
+  for (int a = 0; a < 3; ++a) d[a] = fmaf(t.r[a * 3 + 0], p[0], fmaf(t.r[a * 3 + 1], p[1], fmaf(t.r[a * 3 + 2], p[2], t.t[a]))) - q[a];
+  return fmaf(d[0], d[0], fmaf(d[1], d[1], d[2] * d[2]));
+}
+
+// The pixel an element of the alignment residuals addresses: an index outside the image is clamped to the nearest pixel, so the
+// gather reads no memory outside the frame whatever the caller's indices hold.
+FM_HD int alignment_pixel(long raw, int pixels) { return (int)(raw < 0 ? 0 : (raw >= (long)pixels ? (long)pixels - 1 : raw)); }
+
 // Per-pair constants of the Procrustes backward (produced by the pose-solve backward).
 struct PairGrad {
   float gM[9];      // dL/dM
@@ -1292,4 +1304,5 @@ FM_HD void dense_bwd_s(const DenseBwd& c, const float h[3], const float t[3], co
 #include "fm_flow_bitmask_host.h"
 #include "fm_extrinsics_host.h"
 #include "fm_flow_residuals_host.h"
+#include "fm_alignment_residuals_host.h"
 #endif

@@ -10,7 +10,8 @@ import torch
 from torch import Tensor, nn
 
 from .. import _reference
-from .projection import _align_surfaces
+from ..types import AlignmentResiduals
+from .projection import _align_surfaces, alignment_residuals
 
 
 @dataclass
@@ -78,3 +79,14 @@ class ExtrinsicsProcrustes(nn.Module):
         # (the chain may come back unevaluated — LazyExtrinsics — while gradients are recorded and nothing has read it so far: a flow-only
         # training step reads the fit's relative poses, not the chain)
         return _align_surfaces(surfaces, flows.backward, backbone_output.weights, indices, lazy_ok=True)
+
+    def residuals(self, batch, flows, model_output, pairs=None, indices: Optional[Tensor] = None, offsets: bool = False, weights: bool = False,
+                  sums: bool = True) -> AlignmentResiduals:
+        """The per-element terms of the objective this module's fit minimises (flowmap/model/projection.py:213-252,
+        flowmap/model/procrustes.py:7-51) at the output's own poses — ``projection.alignment_residuals`` over ``model_output``: ``residual`` =
+        ‖T·p − q‖² per pixel (``indices`` None) or per given index, with ``offsets`` the 3-vectors T·p − q, with ``weights`` the
+        correspondence weights used, with ``sums`` Σ w·residual and Σ w per pair in float64, for the pairs ``pairs`` — None (all), a slice
+        with step 1, or (first, count).  ``procrustes_indices(h, w, cfg.num_points, False, device)`` gives this configuration's own
+        deterministic selection.  One launch over depth; never differentiable; reads and nothing else."""
+        return alignment_residuals(model_output.surfaces, flows.backward, model_output.backward_correspondence_weights, model_output.extrinsics,
+                                   indices=indices, pairs=pairs, offsets=offsets, weights=weights, sums=sums)

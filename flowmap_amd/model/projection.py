@@ -22,7 +22,8 @@ import torch
 from torch import Tensor
 
 from .. import _ops
-from .._lib import check_device
+from .._lib import check_device, using_test_double
+from ..types import AlignmentResiduals
 
 # --------------------------------------------------------------------------------------
 # small tensor helpers (no kernels needed: pure indexing / concatenation)
@@ -536,6 +537,98 @@ def align_surfaces(surfaces, backward_flows: Tensor, backward_weights: Tensor, i
     """flowmap/model/projection.py:213-252: per-pair weighted Procrustes on flow-induced
     correspondences, chained into camera-to-world extrinsics (b,f,4,4)."""
     return _align_surfaces(surfaces, backward_flows, backward_weights, indices, lazy_ok=False)
+
+
+def _alignment_pair_window(pairs, total: int):
+    """``pairs`` of alignment_residuals -> (first, count): None (all pairs), a slice with step 1, or (first, count) — the forms of
+    LossFlow.residuals."""
+    if pairs is None:
+        first, count = 0, total
+    elif isinstance(pairs, slice):
+        if pairs.step not in (None, 1):
+            raise ValueError(f"flowmap_amd: alignment_residuals takes a slice of pairs with step 1 (got step {pairs.step})")
+        first, stop, _ = pairs.indices(total)
+        count = stop - first
+    elif isinstance(pairs, (tuple, list)) and len(pairs) == 2 and all(isinstance(x, int) and not isinstance(x, bool) for x in pairs):
+        first, count = pairs
+    else:
+        raise ValueError(f"flowmap_amd: alignment_residuals: pairs must be None, a slice with step 1 or (first, count), got {pairs!r}")
+    if first < 0 or count < 1 or first + count > total:
+        raise ValueError(f"flowmap_amd: alignment_residuals: the pairs [{first}, {first + count}) do not lie in the {total} pairs of the video")
+    return int(first), int(count)
+
+
+def alignment_residuals(surfaces, backward_flows: Tensor, backward_weights, extrinsics, indices: Optional[Tensor] = None, pairs=None,
+                        offsets: bool = False, weights: bool = False, sums: bool = True) -> AlignmentResiduals:
+    """The terms of the objective ``align_surfaces`` minimises per pair (flowmap/model/projection.py:213-252 -> align_rigid,
+    flowmap/model/procrustes.py:7-51): for pair i and element j, with p_j = surfaces[:, i+1] at pixel idx_j, q_j the bilinear,
+    border-clamped sample of surfaces[:, i] at xy[idx_j] + backward_flows[:, i, idx_j], w_j = backward_weights[:, i, idx_j] and
+    T_i = E_i⁻¹·E_{i+1} of ``extrinsics`` (the matrix align_rigid returned when the extrinsics come from the fit):
+    ``offset`` = T_i·[p_j; 1] − q_j, ``residual`` = ‖offset‖² before the weight, ``pair_sum`` = Σ_j w_j·residual_j and
+    ``pair_weight`` = Σ_j w_j in float64.  ``indices`` None: every pixel, maps (b, count, h, w); an int64 tensor of length P (repeats
+    and P > h·w allowed): maps (b, count, P) — the fit's own correspondences when it is the fit's selection
+    (extrinsics_procrustes.procrustes_indices).  ``pairs``: None, a slice with step 1, or (first, count).
+
+    ONE launch (fm_alignment_residuals, plus the small ordered second stage of the sums) that walks the fit's own per-correspondence
+    function over the elements: depth-sourced on a LazySurfaces, surface-sourced on an explicit (b, f, h, w, 3) tensor; nothing of the
+    surfaces' size is formed.  ``backward_weights``: a tensor as it is, a LazyWeights through its logits (the kernel applies the
+    sigmoid), None = weight 1.  Never differentiable, and it only reads: no note on any tensor, no LazyExtrinsics / LazyWeights
+    evaluated, no optimiser or tap state.  Host tensors are refused — the reference has no function that returns this quantity, so
+    there is nothing to hand them to, with or without install()."""
+    with torch.no_grad():
+        lazy = isinstance(surfaces, LazySurfaces)
+        src = surfaces.depths if lazy else surfaces
+        if not torch.is_tensor(src) or not torch.is_tensor(backward_flows):
+            raise RuntimeError("flowmap_amd: alignment_residuals: surfaces must be a LazySurfaces or a tensor, backward_flows a tensor")
+        dev = src.device
+        if dev.type != "cuda" and not using_test_double():
+            raise RuntimeError(f"flowmap_amd: alignment_residuals: tensors are on {dev}; it runs on the GPU only (device 'cuda' on ROCm) — the reference "
+                               "has no function that returns this quantity, so host tensors have nowhere to go. There is no CPU fallback.")
+        if (lazy and src.dim() != 4) or (not lazy and (src.dim() != 5 or src.shape[-1] != 3)):
+            raise RuntimeError(f"flowmap_amd: alignment_residuals: surfaces of shape {tuple(surfaces.shape)}; expected (batch, frame, height, width, 3)")
+        b, f, h, w = src.shape[:4]
+        if tuple(backward_flows.shape) != (b, f - 1, h, w, 2):
+            raise RuntimeError(f"flowmap_amd: alignment_residuals: backward_flows of shape {tuple(backward_flows.shape)} do not match the depths "
+                               f"{(b, f, h, w)}: expected {(b, f - 1, h, w, 2)}")
+        if backward_weights is not None and tuple(backward_weights.shape) != (b, f - 1, h, w):
+            raise RuntimeError(f"flowmap_amd: alignment_residuals: backward_weights of shape {tuple(backward_weights.shape)} do not match the depths "
+                               f"{(b, f, h, w)}: expected {(b, f - 1, h, w)}")
+        if tuple(extrinsics.shape) != (b, f, 4, 4):
+            raise RuntimeError(f"flowmap_amd: alignment_residuals: extrinsics of shape {tuple(extrinsics.shape)} do not match the depths {(b, f, h, w)} "
+                               f"(a depth tensor that holds fewer frames than the poses — a frame shard — is not supported): expected {(b, f, 4, 4)}")
+        if indices is not None:
+            if not torch.is_tensor(indices) or indices.dtype != torch.int64:
+                raise RuntimeError(f"flowmap_amd: alignment_residuals: indices must be an int64 tensor (got {getattr(indices, 'dtype', type(indices).__name__)})")
+            if indices.device != dev:
+                raise RuntimeError(f"flowmap_amd: alignment_residuals: indices are on {indices.device}, the depths on {dev}")
+            if indices.dim() != 1 or indices.numel() == 0:
+                raise RuntimeError(f"flowmap_amd: alignment_residuals: indices must be a non-empty 1-D tensor (got shape {tuple(indices.shape)})")
+        first, count = _alignment_pair_window(pairs, f - 1)
+
+        # T_i = E_i⁻¹·E_{i+1}: the second of the pair the fit leaves on its extrinsics (rel_inv, rel) and of fm_relative_pose_fwd's outputs
+        direct = getattr(extrinsics, "_fm_relative_poses", None)
+        if direct is not None and tuple(direct[1].shape) == (b, f - 1, 4, 4):
+            rel = direct[1].detach()
+        else:
+            ext = extrinsics
+            if isinstance(ext, LazyExtrinsics):  # the chain for this call only: nothing is noted on the flow tensor
+                ext = ext._dense if ext._dense is not None else _ops.PoseChain.apply(ext._rel.detach())
+            rel = _ops.RelativePoses.apply(ext.detach())[1]
+
+        sens = 0.0
+        if isinstance(backward_weights, LazyWeights):
+            if backward_weights.sensitivity != 0.0:
+                backward_weights, sens = backward_weights.logits, backward_weights.sensitivity
+            else:  # (its value, not kept on the object)
+                backward_weights = backward_weights._dense if backward_weights._dense is not None else (0.0 * backward_weights.logits).sigmoid()
+        if backward_weights is not None:
+            backward_weights = backward_weights.detach()
+        if lazy:
+            out = _ops.alignment_residuals(src.detach(), _ops.intrinsics_inverse_peek(surfaces.intrinsics), None, backward_flows, backward_weights, sens, rel,
+                                           indices, first, count, offsets, weights, sums)
+        else:
+            out = _ops.alignment_residuals(None, None, src.detach(), backward_flows, backward_weights, sens, rel, indices, first, count, offsets, weights, sums)
+        return AlignmentResiduals(*out, first)
 
 
 def _align_surfaces(surfaces, backward_flows: Tensor, backward_weights: Tensor, indices: Tensor, lazy_ok: bool):

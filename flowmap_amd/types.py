@@ -7,6 +7,7 @@
   BackboneOutput  flowmap/model/backbone/backbone.py:14-17
   FlowResiduals  what LossFlow.residuals returns (no counterpart in the reference: its loss keeps these maps to itself)
   TrackResiduals  what LossTracking.residuals returns, one per segment (likewise)
+  AlignmentResiduals  what ExtrinsicsProcrustes.residuals returns (likewise: the fit keeps its objective's terms to itself)
 
 The reference's own dataclasses are accepted everywhere these are (duck typing): the
 drop-in never checks the class, only the attribute names.
@@ -120,3 +121,25 @@ class TrackResiduals:
     def track_loss(self) -> Tensor:
         """track_sum / (track_count or 1): each track's own masked mean over all frame pairs."""
         return self._ratio(self.track_sum, self.track_count, "track_loss")
+
+
+@dataclass
+class AlignmentResiduals:
+    """The terms of the objective the Procrustes fit minimises, Σ w‖T·p − q‖² (flowmap/model/procrustes.py:7-51) over the correspondences
+    of align_surfaces (flowmap/model/projection.py:213-252), for the pairs [first_pair, first_pair + count) —
+    ExtrinsicsProcrustes.residuals.  ``maps`` is (batch, count, H, W) over every pixel, or (batch, count, P) over P indices."""
+
+    residual: Tensor  # maps: ‖T·[p; 1] − q‖², before the weight
+    offset: Optional[Tensor]  # maps + (3,): T·[p; 1] − q in the earlier camera's space; None unless asked for
+    weight: Optional[Tensor]  # maps: the weight the kernel used (the sigmoid it applied to lazy logits; 1 without weights); None unless asked for
+    pair_sum: Optional[Tensor]  # (batch, count) float64: Σ weight·residual per pair; None unless asked for
+    pair_weight: Optional[Tensor]  # (batch, count) float64: Σ weight
+    first_pair: int
+
+    def pair_loss(self) -> Tensor:
+        """pair_sum / (pair_weight or 1): each pair's own weighted mean."""
+        if self.pair_sum is None:
+            raise RuntimeError("flowmap_amd: AlignmentResiduals.pair_loss needs the sums (ExtrinsicsProcrustes.residuals(..., sums=True))")
+        from .loss.loss import or_one
+
+        return self.pair_sum / or_one(self.pair_weight)

@@ -43,8 +43,9 @@ extern "C" {
  * loss — fm_flow_masks_binary, fm_flow_pack_inputs_bitmask(_views), fm_flow_loss_fused_bitmask; the existing entries are unchanged; version 8: the regressed
  * extrinsics — fm_quat_pose_fwd / fm_quat_pose_bwd; the existing entries are unchanged; version 9: the flow residual maps —
  * fm_flow_residuals / fm_flow_residual_blocks; the existing entries are unchanged; version 10: the tracking residual maps —
- * fm_track_residuals / fm_track_residual_workspace; the existing entries are unchanged).  A binding checks fm_abi_version() == FM_ABI_VERSION when it loads the library. */
-#define FM_ABI_VERSION 10
+ * fm_track_residuals / fm_track_residual_workspace; the existing entries are unchanged; version 11: the alignment residual maps —
+ * fm_alignment_residuals / fm_alignment_residual_workspace; the existing entries are unchanged).  A binding checks fm_abi_version() == FM_ABI_VERSION when it loads the library. */
+#define FM_ABI_VERSION 11
 int fm_abi_version(void);
 
 #define FM_STAT_STRIDE 16      /* doubles per pair in `stats` */
@@ -789,6 +790,41 @@ int fm_track_residuals(const float* depth, const float* kinv, const float* ext, 
                        int mapping_kind, float delta, float aspect_x, float aspect_y, float* tgt, float* residual, uint8_t* visible,
                        float* xy_target, double* pair_sum, double* pair_count, double* track_sum, double* track_count, double* workspace,
                        void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Alignment residual maps (ABI version 11).  The terms of the objective the Procrustes fit minimises, Σ w‖T·p − q‖²
+ * (flowmap/model/procrustes.py:7-51), over the correspondences align_surfaces builds (flowmap/model/projection.py:213-252), per
+ * element and per pair, for a window of pairs, in ONE pass: p = xyz of frame i+1 at the pixel (projection.py:226-227), q = the
+ * bilinear, border-clamped, align_corners=False sample of frame i's xyz at xy + backward flow (projection.py:231-242), w the
+ * correspondence weight (projection.py:245-249) — fm_math.h: corr_load_with, the fit's own per-correspondence function.
+ *
+ *   depth (B,F,H,W) + kinv (B,F,3,3) [depth-sourced], or surfaces (B,F,H,W,3) [surface-sourced]; exactly one of depth / surfaces
+ *     is non-NULL (kinv goes with depth).  bwd_flow (B,F-1,H,W,2).  All dense, the WHOLE stacks.
+ *   weights (B,F-1,H,W), or NULL = weight 1 everywhere; with weight_sensitivity != 0 they are logits and
+ *     w = sigmoid(weight_sensitivity · logit) (flowmap/model/backbone/backbone_explicit_depth.py:38-41).
+ *   rel (B,F-1,4,4): T_i = E_i⁻¹·E_{i+1}, camera i+1 -> camera i — what align_rigid returns (projection.py:245-249), the `bwd`
+ *     output of fm_relative_pose_fwd.
+ *   indices (points) int64 DEVICE, or NULL = element j is pixel j (then points must be H·W).  Repeated indices and
+ *     points > H·W are fine (extrinsics_procrustes.py:34-51 draws them with randint).  An index outside [0, H·W) is clamped to
+ *     the nearest pixel: the call reads no memory outside its arguments whatever the indices hold.
+ *   first_pair, count: the pairs [first_pair, first_pair + count) of every batch entry, 0 <= first_pair, count >= 1,
+ *     first_pair + count <= F - 1, B·count <= 65535.  1 <= points < 2^30, H·W < 2^30.
+ *   residual (B,count,points) out: ‖T·[p;1] − q‖², before the weight.
+ *   offset (B,count,points,3) out or NULL: T·[p;1] − q, in camera i's space.
+ *   weight_out (B,count,points) out or NULL: the w the kernel used (the sigmoid it applied, or 1).
+ *   pair_sum, pair_weight (B,count) doubles out, or both NULL: Σ (double)(w·residual) — the fp32 product, converted — and
+ *     Σ (double)w per pair, in fp64 from the element upward WITHOUT atomics: every workgroup leaves its partial in `workspace` —
+ *     fm_alignment_residual_workspace(points)·B·count doubles, 16-byte aligned, contents unspecified on entry and on return —
+ *     and a second small launch adds a pair's partials in ascending workgroup order.  Which elements a workgroup owns depends
+ *     on `points` only: the sums are bit-reproducible, and bit-identical whether a pair is reached through the full range or a window.
+ * EVERY element of every output is written (no zero fill beforehand).
+ *
+ * fm_alignment_residual_workspace: doubles[0] (HOST long) = workspace doubles of ONE (batch entry, pair) at `points` elements. */
+int fm_alignment_residual_workspace(long points, long* doubles);
+int fm_alignment_residuals(const float* depth, const float* kinv, const float* surfaces, const float* bwd_flow, const float* weights,
+                           float weight_sensitivity, const float* rel, const int64_t* indices, long points, int batch, int frames,
+                           int height, int width, int first_pair, int count, float* residual, float* offset, float* weight_out,
+                           double* pair_sum, double* pair_weight, double* workspace, void* stream);
 
 #ifdef __cplusplus
 }
