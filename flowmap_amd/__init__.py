@@ -24,9 +24,9 @@ from .graph import GraphedShardedStep, GraphedStep  # noqa: F401
 from .host import freeze_gc  # noqa: F401
 from ._ops import release_flow_originals  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
-from .types import AlignmentResiduals, BackboneOutput, Batch, FlowResiduals, Flows, ModelOutput, TrackResiduals, Tracks  # noqa: F401
+from .types import AlignmentResiduals, BackboneOutput, Batch, FlowResiduals, Flows, FocalSweep, ModelOutput, TrackResiduals, Tracks  # noqa: F401
 
 __all__ = [
     "config", "loss", "model", "install", "uninstall", "set_lazy_surfaces", "FusedAdam", "GraphedStep", "GraphedShardedStep", "freeze_gc", "release_flow_originals",
-    "Batch", "BackboneOutput", "AlignmentResiduals", "FlowResiduals", "TrackResiduals", "Flows", "ModelOutput", "Tracks", "ExtrinsicsRegressed", "ExtrinsicsRegressedCfg",
+    "Batch", "BackboneOutput", "AlignmentResiduals", "FlowResiduals", "FocalSweep", "TrackResiduals", "Flows", "ModelOutput", "Tracks", "ExtrinsicsRegressed", "ExtrinsicsRegressedCfg",
 ]

@@ -122,6 +122,7 @@ SIGNATURES = {
     "fm_track_residuals": [P] * 5 + [I, P, P, P, I, I, I, I, I, I, I, F, F, F] + [P] * 10,
     "fm_alignment_residual_workspace": [L, P],
     "fm_alignment_residuals": [P] * 5 + [F, P, P, L, I, I, I, I, I, I] + [P] * 7,
+    "fm_focal_sweep": [P, P, F, P, P, L, P, P, P, I, I, I, I, I, I, I] + [P] * 7,
 }
 
 _lib: Optional[ctypes.CDLL] = None

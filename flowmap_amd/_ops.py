@@ -241,7 +241,7 @@ def _dense_flow_is_rough(bwd_flow: Tensor, h: int, w: int) -> bool:
 
 # which backward path the facades selected (tests)
 counters = {"procrustes_planned": 0, "procrustes_dense_planned": 0, "flow_packs": 0, "flow_packs_bitmask": 0, "procrustes_plans_built": 0, "track_tap_samples": 0,
-            "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0, "flow_residuals": 0, "track_residuals": 0, "alignment_residuals": 0}
+            "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0, "flow_residuals": 0, "track_residuals": 0, "alignment_residuals": 0, "focal_sweep": 0}
 
 
 class LeadingFrames:
@@ -821,6 +821,50 @@ def alignment_residuals(depth, kinv, surfaces, bwd_flow, weights, weight_sens, r
              ptr(residual), ptr(offset), ptr(weight), ptr(pair_sum), ptr(pair_weight), ptr(work), stream_for(src))
     counters["alignment_residuals"] += 1
     return residual, offset, weight, pair_sum, pair_weight
+
+
+def focal_sweep(depth, weights, weight_sens, bwd_flow, indices, focal_lengths, candidate_k, candidate_kinv, first_pair, count, poses, points):
+    """The softmin focal sweep of the pairs [first_pair, first_pair + count) (fm_focal_sweep): (error (b, count, n) float64, soft (b, count, n),
+    focal (b, count), intrinsics (b, count, 3, 3), poses (b, count, n, 4, 4) or None, point_error (b, count, n, P) or None).  ``weights``: a
+    tensor, or logits with ``weight_sens`` != 0; ``indices`` int64 (P).  Two ordered launches.  Reads its arguments and nothing else: no
+    DepthSink, no LeadingFrames, no note on any tensor, no random state."""
+    dev = check_device(depth, weights, bwd_flow, indices, focal_lengths, candidate_k, candidate_kinv)
+    depth, weights, bwd_flow = _f32c(depth, "depth"), _f32c(weights, "correspondence weights"), _f32c(bwd_flow, "backward flow")
+    focal_lengths, candidate_k, candidate_kinv = _f32c(focal_lengths, "focal length candidates"), _f32c(candidate_k, "candidate intrinsics"), _f32c(candidate_kinv, "inverse candidate intrinsics")
+    if depth.dim() != 4:
+        raise RuntimeError("flowmap_amd: depth must be (batch, frame, height, width)")
+    b, f, h, w = depth.shape
+    if tuple(bwd_flow.shape) != (b, f - 1, h, w, 2):
+        raise RuntimeError(f"flowmap_amd: flow shape {tuple(bwd_flow.shape)} does not match depth {(b, f, h, w)}")
+    if tuple(weights.shape) != (b, f - 1, h, w):
+        raise RuntimeError(f"flowmap_amd: weight shape {tuple(weights.shape)} does not match depth {(b, f, h, w)}")
+    n = focal_lengths.numel()
+    if focal_lengths.dim() != 1 or n < 1 or tuple(candidate_k.shape) != (n, 3, 3) or tuple(candidate_kinv.shape) != (n, 3, 3):
+        raise RuntimeError(f"flowmap_amd: the focal sweep takes candidates (n), K (n, 3, 3) and K^-1 (n, 3, 3); got {tuple(focal_lengths.shape)}, "
+                           f"{tuple(candidate_k.shape)}, {tuple(candidate_kinv.shape)}")
+    if h * w >= 1 << 30:
+        raise RuntimeError(f"flowmap_amd: the focal sweep indexes pixels inside a frame with 32 bits: height x width = {h * w} must stay below 2^30")
+    if first_pair < 0 or count < 1 or first_pair + count > f - 1:
+        raise RuntimeError(f"flowmap_amd: the pair window [{first_pair}, {first_pair + count}) does not lie in the {f - 1} pairs")
+    if b * count > 65535:
+        raise RuntimeError(f"flowmap_amd: the focal sweep handles at most 65 535 pairs per call (batch x pairs = {b * count}): split the window")
+    indices = indices.contiguous()
+    p = indices.numel()
+    if indices.dtype != torch.int64 or indices.dim() != 1 or not 1 <= p < 1 << 30:
+        raise RuntimeError(f"flowmap_amd: the focal sweep takes between 1 and 2^30 - 1 int64 indices (got {tuple(indices.shape)} {indices.dtype})")
+    f32 = dict(dtype=torch.float32, device=dev)
+    error = torch.empty((b, count, n), dtype=torch.float64, device=dev)
+    soft = torch.empty((b, count, n), **f32)
+    focal = torch.empty((b, count), **f32)
+    intrinsics = torch.empty((b, count, 3, 3), **f32)
+    pose_out = torch.empty((b, count, n, 4, 4), **f32) if poses else None
+    point_error = torch.empty((b, count, n, p), **f32) if points else None
+    with _guard(dev):
+        call("fm_focal_sweep", ptr(depth), ptr(weights), float(weight_sens), ptr(bwd_flow), ptr(indices), p, ptr(focal_lengths), ptr(candidate_k),
+             ptr(candidate_kinv), b, f, h, w, int(first_pair), int(count), n, ptr(error), ptr(soft), ptr(focal), ptr(intrinsics), ptr(pose_out),
+             ptr(point_error), stream_for(depth))
+    counters["focal_sweep"] += 1
+    return error, soft, focal, intrinsics, pose_out, point_error
 
 
 def softmin_intrinsics(depth, weights, bwd_flow, indices, candidate_k, rel, weight_sens, frames):

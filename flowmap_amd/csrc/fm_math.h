@@ -1305,4 +1305,5 @@ FM_HD void dense_bwd_s(const DenseBwd& c, const float h[3], const float t[3], co
 #include "fm_extrinsics_host.h"
 #include "fm_flow_residuals_host.h"
 #include "fm_alignment_residuals_host.h"
+#include "fm_focal_sweep_host.h"
 #endif

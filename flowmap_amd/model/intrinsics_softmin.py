@@ -24,7 +24,8 @@ from torch import Tensor, nn
 
 from .. import _ops, _reference
 from .model import IntrinsicsRegressed, IntrinsicsRegressedCfg, focal_lengths_to_intrinsics
-from .projection import LazyWeights
+from ..types import FocalSweep
+from .projection import LazyWeights, focal_sweep
 
 
 @dataclass
@@ -147,6 +148,30 @@ class IntrinsicsSoftmin(nn.Module):
             self.window.append((self.focal_length_candidates * soft).sum().detach())
 
         return intrinsics
+
+    def residuals(self, batch, flows, backbone_output, pairs=None, indices: Optional[Tensor] = None, seed: int = 0, points: bool = False,
+                  poses: bool = True) -> FocalSweep:
+        """The sweep ``forward`` runs on frames (0, 1), for every pair of ``pairs`` (None, a slice with step 1 or (first, count); pair i is
+        frames (i, i+1)) and with what ``forward`` drops kept — a FocalSweep: per candidate the error and the fitted pose, per pair the
+        softmin weights, the blended focal length (what the reference appends to its window) and the blended K (what ``forward`` returns
+        per frame); with ``points`` the per-point terms.  ``backbone_output``: anything with ``.depths`` and ``.weights`` or
+        ``.backward_correspondence_weights`` (a BackboneOutput or a ModelOutput).  ``indices``: int64 pixel indices, or None:
+        min(cfg.num_procrustes_points, h·w) of them drawn with the explicit ``seed`` — no generator is advanced.
+
+        projection.focal_sweep with this module's candidates: one call of fm_focal_sweep.  It takes no ``global_step`` and works before
+        and after the hand-over to the regressed stage; it never touches ``self.window``, the leading-frame or touched-pixel notes,
+        gradients or parameters.  Host tensors are refused (there is no CPU fallback), and so is a module whose frame shard is active."""
+        if self.shard is not None and self.shard.active:
+            raise RuntimeError("flowmap_amd: IntrinsicsSoftmin.residuals: this module's frame shard is active (flowmap_amd.sharding): a rank holds its own "
+                               "frames only, and sharded sweeps are not supported — call it on an unsharded model")
+        weights = getattr(backbone_output, "weights", None)
+        if weights is None:
+            weights = getattr(backbone_output, "backward_correspondence_weights", None)
+        depths = getattr(backbone_output, "depths", None)
+        if depths is None or weights is None:
+            raise RuntimeError("flowmap_amd: IntrinsicsSoftmin.residuals: backbone_output needs .depths and .weights or .backward_correspondence_weights")
+        return focal_sweep(depths, weights, flows.backward, self.focal_length_candidates, pairs=pairs, indices=indices, seed=seed, points=points,
+                           poses=poses, num_points=self.cfg.num_procrustes_points)
 
     def unnormalized_focal_lengths(self, image_shape) -> Tensor:
         """intrinsics_softmin.py:143-156"""

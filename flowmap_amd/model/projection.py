@@ -23,7 +23,7 @@ from torch import Tensor
 
 from .. import _ops
 from .._lib import check_device, using_test_double
-from ..types import AlignmentResiduals
+from ..types import AlignmentResiduals, FocalSweep
 
 # --------------------------------------------------------------------------------------
 # small tensor helpers (no kernels needed: pure indexing / concatenation)
@@ -629,6 +629,71 @@ def alignment_residuals(surfaces, backward_flows: Tensor, backward_weights, extr
         else:
             out = _ops.alignment_residuals(None, None, src.detach(), backward_flows, backward_weights, sens, rel, indices, first, count, offsets, weights, sums)
         return AlignmentResiduals(*out, first)
+
+
+def focal_sweep(depths: Tensor, weights, backward_flow: Tensor, focal_length_candidates: Tensor, pairs=None, indices: Optional[Tensor] = None,
+                seed: int = 0, points: bool = False, poses: bool = True, num_points: Optional[int] = None) -> FocalSweep:
+    """The softmin focal sweep (flowmap/model/intrinsics/intrinsics_softmin.py:85-141) of every pair of ``pairs`` — None (all), a slice with
+    step 1 or (first, count), the forms of LossFlow.residuals; pair i is frames (i, i+1) — instead of pair 0 only, with what the reference
+    drops kept: per candidate the error (float64) and the fitted pose of frame i+1 in frame i's space, per pair the softmin weights, the
+    blended focal length and the blended K; with ``points`` the per-point term.  ``depths`` (b, f, h, w); ``weights`` (b, f-1, h, w), a tensor
+    or a LazyWeights (its logits go to the kernel when its sensitivity is not 0, its value otherwise); ``backward_flow`` (b, f-1, h, w, 2);
+    ``focal_length_candidates`` (n).  ``indices``: an int64 tensor of P pixel indices (one outside the image is clamped), or None:
+    min(num_points, h·w) of them from ``_ops.random_subset(..., seed=seed)`` — an explicit seed, so the call advances no random state.
+
+    ONE call of fm_focal_sweep: a launch with a workgroup per (batch entry, pair, candidate) that fits and scores from depth, and a launch
+    with a wave per (batch entry, pair) for the curve.  Never differentiable, and it only reads: no LeadingFrames, no note on any tensor,
+    no LazyWeights evaluated, no generator advanced.  Host tensors are refused — the reference has no function that returns this."""
+    with torch.no_grad():
+        if not torch.is_tensor(depths) or not torch.is_tensor(backward_flow) or not torch.is_tensor(focal_length_candidates):
+            raise RuntimeError("flowmap_amd: focal_sweep: depths, backward_flow and focal_length_candidates must be tensors")
+        dev = depths.device
+        if dev.type != "cuda" and not using_test_double():
+            raise RuntimeError(f"flowmap_amd: focal_sweep: tensors are on {dev}; it runs on the GPU only (device 'cuda' on ROCm) — the reference has no "
+                               "function that returns this quantity, so host tensors have nowhere to go. There is no CPU fallback.")
+        if depths.dim() != 4:
+            raise RuntimeError(f"flowmap_amd: focal_sweep: depths of shape {tuple(depths.shape)}; expected (batch, frame, height, width)")
+        b, f, h, w = depths.shape
+        if tuple(backward_flow.shape) != (b, f - 1, h, w, 2):
+            raise RuntimeError(f"flowmap_amd: focal_sweep: backward_flow of shape {tuple(backward_flow.shape)} does not match the depths {(b, f, h, w)}: "
+                               f"expected {(b, f - 1, h, w, 2)}")
+        if weights is None or tuple(weights.shape) != (b, f - 1, h, w):
+            raise RuntimeError(f"flowmap_amd: focal_sweep: weights of shape {None if weights is None else tuple(weights.shape)} do not match the depths "
+                               f"{(b, f, h, w)}: expected {(b, f - 1, h, w)}")
+        if focal_length_candidates.dim() != 1 or focal_length_candidates.numel() < 1:
+            raise RuntimeError(f"flowmap_amd: focal_sweep: focal_length_candidates must be a non-empty 1-D tensor (got shape {tuple(focal_length_candidates.shape)})")
+        for name, value in (("depths", depths), ("backward_flow", backward_flow), ("focal_length_candidates", focal_length_candidates),
+                            ("weights", weights.logits if isinstance(weights, LazyWeights) else weights)):
+            if value.dtype != torch.float32:
+                raise RuntimeError(f"flowmap_amd: focal_sweep: {name} must be float32 (got {value.dtype})")
+        if indices is not None:
+            if not torch.is_tensor(indices) or indices.dtype != torch.int64:
+                raise RuntimeError(f"flowmap_amd: focal_sweep: indices must be an int64 tensor (got {getattr(indices, 'dtype', type(indices).__name__)})")
+            if indices.device != dev:
+                raise RuntimeError(f"flowmap_amd: focal_sweep: indices are on {indices.device}, the depths on {dev}")
+            if indices.dim() != 1 or indices.numel() == 0:
+                raise RuntimeError(f"flowmap_amd: focal_sweep: indices must be a non-empty 1-D tensor (got shape {tuple(indices.shape)})")
+        from ..loss.loss_flow import LossFlow  # (the one parser of ``pairs``; imported here: the loss modules import this one)
+
+        first, count = LossFlow._pair_window(pairs, f - 1)
+        if b * count > 65535:
+            raise ValueError(f"flowmap_amd: focal_sweep: batch x pairs = {b * count} exceeds the 65 535 (batch entry, pair) rows of one call: "
+                             "ask for a window of pairs")
+        if indices is None:
+            indices = _ops.random_subset(h * w, min(h * w if num_points is None else int(num_points), h * w), dev, seed=int(seed))
+        sens = 0.0
+        if isinstance(weights, LazyWeights):
+            if weights.sensitivity != 0.0:
+                weights, sens = weights.logits, weights.sensitivity
+            else:  # (its value, not kept on the object)
+                weights = weights._dense if weights._dense is not None else (0.0 * weights.logits).sigmoid()
+        from .model import focal_lengths_to_intrinsics
+
+        candidates = focal_length_candidates.detach()
+        candidate_k = focal_lengths_to_intrinsics(candidates, (h, w))
+        out = _ops.focal_sweep(depths.detach(), weights.detach(), sens, backward_flow.detach(), indices, candidates, candidate_k,
+                               _ops.intrinsics_inverse_peek(candidate_k), first, count, poses, points)
+        return FocalSweep(first, count, candidates, indices, *out)
 
 
 def _align_surfaces(surfaces, backward_flows: Tensor, backward_weights: Tensor, indices: Tensor, lazy_ok: bool):

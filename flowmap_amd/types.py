@@ -8,6 +8,7 @@
   FlowResiduals  what LossFlow.residuals returns (no counterpart in the reference: its loss keeps these maps to itself)
   TrackResiduals  what LossTracking.residuals returns, one per segment (likewise)
   AlignmentResiduals  what ExtrinsicsProcrustes.residuals returns (likewise: the fit keeps its objective's terms to itself)
+  FocalSweep  what IntrinsicsSoftmin.residuals returns (likewise: the sweep keeps its error curve and per-candidate poses to itself)
 
 The reference's own dataclasses are accepted everywhere these are (duck typing): the
 drop-in never checks the class, only the attribute names.
@@ -143,3 +144,21 @@ class AlignmentResiduals:
         from .loss.loss import or_one
 
         return self.pair_sum / or_one(self.pair_weight)
+
+
+@dataclass
+class FocalSweep:
+    """The softmin focal sweep (flowmap/model/intrinsics/intrinsics_softmin.py:85-141) of the pairs [first_pair, first_pair + count), pair i
+    being frames (i, i+1), over n focal-length candidates on P sampled pixels — IntrinsicsSoftmin.residuals.  The reference evaluates
+    pair 0 only and keeps nothing but the blended K."""
+
+    first_pair: int
+    count: int
+    focal_lengths: Tensor  # (n) float32: the candidates
+    indices: Tensor  # (P) int64: the pixel indices used
+    error: Tensor  # (batch, count, n) float64: Σ over the points of |w·Δflow_x| + |w·Δflow_y| (intrinsics_softmin.py:124-125), per pair
+    soft: Tensor  # (batch, count, n) float32: softmin((error − min)·10)
+    focal: Tensor  # (batch, count) float32: Σ candidates·soft — what the reference appends to its window
+    intrinsics: Tensor  # (batch, count, 3, 3) float32: Σ soft·K_candidate — what forward returns per frame
+    poses: Optional[Tensor]  # (batch, count, n, 4, 4) float32: the fitted relative pose per candidate, later -> earlier; None unless asked for
+    point_error: Optional[Tensor]  # (batch, count, n, P) float32: the per-point term before the sum; None unless asked for

@@ -44,8 +44,9 @@ extern "C" {
  * extrinsics — fm_quat_pose_fwd / fm_quat_pose_bwd; the existing entries are unchanged; version 9: the flow residual maps —
  * fm_flow_residuals / fm_flow_residual_blocks; the existing entries are unchanged; version 10: the tracking residual maps —
  * fm_track_residuals / fm_track_residual_workspace; the existing entries are unchanged; version 11: the alignment residual maps —
- * fm_alignment_residuals / fm_alignment_residual_workspace; the existing entries are unchanged).  A binding checks fm_abi_version() == FM_ABI_VERSION when it loads the library. */
-#define FM_ABI_VERSION 11
+ * fm_alignment_residuals / fm_alignment_residual_workspace; the existing entries are unchanged; version 12: the softmin focal sweep per
+ * pair — fm_focal_sweep; the existing entries are unchanged).  A binding checks fm_abi_version() == FM_ABI_VERSION when it loads the library. */
+#define FM_ABI_VERSION 12
 int fm_abi_version(void);
 
 #define FM_STAT_STRIDE 16      /* doubles per pair in `stats` */
@@ -825,6 +826,31 @@ int fm_alignment_residuals(const float* depth, const float* kinv, const float* s
                            float weight_sensitivity, const float* rel, const int64_t* indices, long points, int batch, int frames,
                            int height, int width, int first_pair, int count, float* residual, float* offset, float* weight_out,
                            double* pair_sum, double* pair_weight, double* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * The softmin focal sweep, per frame pair (ABI version 12).  What IntrinsicsSoftmin evaluates on frames (0, 1) and reduces to one K
+ * (flowmap/model/intrinsics/intrinsics_softmin.py:85-141), kept per candidate and computed for a WINDOW of pairs: for batch entry b,
+ * pair i = frames (i, i+1) and candidate c, the Procrustes fit of the pair's correspondences under K_c for both frames
+ * (projection.py:213-252, procrustes.py:7-51; fm_math.h: corr_load_with, moments_add; fm_pose.h: pose_solve_one) and
+ * error = Σ_j |w_j·(flow_x − gt_x)| + |w_j·(flow_y − gt_y)| of the pose-induced backward flow (intrinsics_softmin.py:105-125;
+ * fm_math.h: softmin_term); then soft = softmin((error − min error)·10) over the candidates in fp32, K = Σ soft·K_c and
+ * focal = Σ soft·focal_c.  Two launches on `stream`, ordered; depth-sourced only.
+ *
+ *   depth (B,F,H,W), weights (B,F-1,H,W) — with weight_sensitivity != 0 logits, w = sigmoid(weight_sensitivity · logit) —
+ *   bwd_flow (B,F-1,H,W,2): all dense, the WHOLE stacks.
+ *   indices (points) int64 DEVICE, 1 <= points < 2^30; an index outside [0, H·W) is clamped to the nearest pixel.
+ *   focal_lengths (N), candidate_k (N,3,3), candidate_kinv (N,3,3): the candidates, their K and K⁻¹; N = candidates >= 1.
+ *   first_pair, count: the pairs [first_pair, first_pair + count) of every batch entry, 0 <= first_pair, count >= 1,
+ *     first_pair + count <= F - 1, B·count <= 65535.  H·W < 2^30.
+ *   error (B,count,N) doubles out; soft (B,count,N), focal (B,count), intrinsics (B,count,3,3) out.
+ *   poses (B,count,N,4,4) out or NULL: the fitted pose per candidate, camera i+1 -> camera i.
+ *   point_error (B,count,N,points) out or NULL: the per-point term before the sum.
+ * One workgroup owns one element of `error`: no atomics, no workspace; the results are bit-reproducible and bit-identical whether a
+ * pair is reached through the full range or a window.  EVERY element of every output is written. */
+int fm_focal_sweep(const float* depth, const float* weights, float weight_sensitivity, const float* bwd_flow, const int64_t* indices, long points,
+                   const float* focal_lengths, const float* candidate_k, const float* candidate_kinv, int batch, int frames, int height, int width,
+                   int first_pair, int count, int candidates, double* error, float* soft, float* focal, float* intrinsics, float* poses,
+                   float* point_error, void* stream);
 
 #ifdef __cplusplus
 }
