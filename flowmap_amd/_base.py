@@ -1,6 +1,6 @@
 """Shared plumbing of the operator modules (flowmap_amd/_ops.py and its parts): the C ABI's layout constants, the device flags a backward
-raises when a loss reached it scaled, dtype / contiguity checks, the fm_layout description of frame windows, the device guard and the
-"derived data lives on the tensor it was derived from" helper.  No operator lives here."""
+raises when a loss reached it scaled, the window parser of the residual calls, dtype / contiguity checks, the fm_layout description of
+frame windows, the device guard and the "derived data lives on the tensor it was derived from" helper.  No operator lives here."""
 
 from __future__ import annotations
 
@@ -44,6 +44,31 @@ def check_unit_flags(what: str) -> None:
             raise RuntimeError(f"flowmap_amd: {what}: a loss reached backward() with an upstream gradient other than 1 although its unscaled gradient had "
                                "already been used (FusedAdam.fuse_depth_update applied it inside the flow pass / FrameShard.enable_early_halo sent it before "
                                "backward): the affected steps are wrong.  Switch those options off for a scaled or averaged loss.")
+
+
+def parse_window(selection, total: int, what: str, noun: str, allow_int: bool = False):
+    """The ``pairs`` / ``segments`` argument of the residual calls -> (first, count) inside [0, total): None (all of them), a slice with
+    step 1, (first, count) as a tuple or list, and — with ``allow_int`` — one int (negative: from the end).  ``what`` names the caller in
+    the ValueError, ``noun`` what is being selected ("pairs", "segments")."""
+    forms = f"None, {'an int, ' if allow_int else ''}a slice with step 1 or (first, count)"
+    is_int = lambda x: isinstance(x, int) and not isinstance(x, bool)  # noqa: E731
+    if selection is None:
+        first, count = 0, total
+    elif allow_int and is_int(selection):
+        first, count = (selection + total if selection < 0 else selection), 1
+    elif isinstance(selection, slice):
+        if selection.step not in (None, 1):
+            raise ValueError(f"flowmap_amd: {what} takes a slice of {noun} with step 1 (got step {selection.step})")
+        first, stop, _ = selection.indices(total)
+        count = stop - first
+    elif isinstance(selection, (tuple, list)) and len(selection) == 2 and all(is_int(x) for x in selection):
+        first, count = selection
+    else:
+        raise ValueError(f"flowmap_amd: {what}: {noun} must be {forms}, got {selection!r}")
+    if first < 0 or count < 1 or first + count > total:
+        where = "the video" if noun == "pairs" else "the track list"
+        raise ValueError(f"flowmap_amd: {what}: the {noun} [{first}, {first + count}) do not lie in the {total} {noun} of {where}")
+    return int(first), int(count)
 
 
 def _f32c(t: Tensor, what: str) -> Tensor:

@@ -762,6 +762,31 @@ def track_residuals(depth, k, ext, packed, first, count, kind, delta, predicted,
     return out
 
 
+def _check_pair_call(noun: str, plural: bool, depth, surfaces, bwd_flow, weights, first_pair, count) -> tuple:
+    """What the per-pair diagnostics (alignment_residuals, focal_sweep) check alike -> (b, f, h, w): the rank of the depth (or, without one,
+    of the surfaces), the flow and weight shapes, the 32-bit pixel index, the window and the rows of one call.  ``noun`` ("the focal
+    sweep") and its number go into the texts."""
+    if depth is not None:
+        if depth.dim() != 4:
+            raise RuntimeError("flowmap_amd: depth must be (batch, frame, height, width)")
+        b, f, h, w = depth.shape
+    else:
+        if surfaces.dim() != 5 or surfaces.shape[-1] != 3:
+            raise RuntimeError("flowmap_amd: surfaces must be (batch, frame, height, width, 3)")
+        b, f, h, w, _ = surfaces.shape
+    if tuple(bwd_flow.shape) != (b, f - 1, h, w, 2):
+        raise RuntimeError(f"flowmap_amd: flow shape {tuple(bwd_flow.shape)} does not match depth {(b, f, h, w)}")
+    if weights is not None and tuple(weights.shape) != (b, f - 1, h, w):
+        raise RuntimeError(f"flowmap_amd: weight shape {tuple(weights.shape)} does not match depth {(b, f, h, w)}")
+    if h * w >= 1 << 30:
+        raise RuntimeError(f"flowmap_amd: {noun} {'index' if plural else 'indexes'} pixels inside a frame with 32 bits: height x width = {h * w} must stay below 2^30")
+    if first_pair < 0 or count < 1 or first_pair + count > f - 1:
+        raise RuntimeError(f"flowmap_amd: the pair window [{first_pair}, {first_pair + count}) does not lie in the {f - 1} pairs")
+    if b * count > 65535:
+        raise RuntimeError(f"flowmap_amd: {noun} {'handle' if plural else 'handles'} at most 65 535 pairs per call (batch x pairs = {b * count}): split the window")
+    return b, f, h, w
+
+
 def alignment_residuals(depth, kinv, surfaces, bwd_flow, weights, weight_sens, rel, indices, first_pair, count, offsets, weight_map, sums):
     """The terms of the Procrustes fit's objective for the pairs [first_pair, first_pair + count) (fm_alignment_residuals): (residual,
     offset, weight, pair_sum, pair_weight), None for what was not asked for, shaped (b, count, P[, 3]) and (b, count).  ``depth`` +
@@ -772,31 +797,16 @@ def alignment_residuals(depth, kinv, surfaces, bwd_flow, weights, weight_sens, r
     dev = check_device(src, kinv, bwd_flow, weights, rel, indices)
     if depth is not None:
         depth, kinv = _f32c(depth, "depth"), _f32c(kinv, "inverse intrinsics")
-        if depth.dim() != 4:
-            raise RuntimeError("flowmap_amd: depth must be (batch, frame, height, width)")
-        b, f, h, w = depth.shape
-        if tuple(kinv.shape) != (b, f, 3, 3):
-            raise RuntimeError(f"flowmap_amd: intrinsics shape {tuple(kinv.shape)} does not match depth {tuple(depth.shape)}")
     else:
         surfaces = _f32c(surfaces, "surfaces")
-        if surfaces.dim() != 5 or surfaces.shape[-1] != 3:
-            raise RuntimeError("flowmap_amd: surfaces must be (batch, frame, height, width, 3)")
-        b, f, h, w, _ = surfaces.shape
     bwd_flow, rel = _f32c(bwd_flow, "backward flow"), _f32c(rel, "relative poses")
-    if tuple(bwd_flow.shape) != (b, f - 1, h, w, 2):
-        raise RuntimeError(f"flowmap_amd: flow shape {tuple(bwd_flow.shape)} does not match depth {(b, f, h, w)}")
     if weights is not None:
         weights = _f32c(weights, "correspondence weights")
-        if tuple(weights.shape) != (b, f - 1, h, w):
-            raise RuntimeError(f"flowmap_amd: weight shape {tuple(weights.shape)} does not match depth {(b, f, h, w)}")
+    b, f, h, w = _check_pair_call("the alignment residuals", True, depth, surfaces, bwd_flow, weights, first_pair, count)
+    if depth is not None and tuple(kinv.shape) != (b, f, 3, 3):
+        raise RuntimeError(f"flowmap_amd: intrinsics shape {tuple(kinv.shape)} does not match depth {tuple(depth.shape)}")
     if tuple(rel.shape) != (b, f - 1, 4, 4):
         raise RuntimeError(f"flowmap_amd: pose shape {tuple(rel.shape)} does not match depth {(b, f, h, w)}")
-    if h * w >= 1 << 30:
-        raise RuntimeError(f"flowmap_amd: the alignment residuals index pixels inside a frame with 32 bits: height x width = {h * w} must stay below 2^30")
-    if first_pair < 0 or count < 1 or first_pair + count > f - 1:
-        raise RuntimeError(f"flowmap_amd: the pair window [{first_pair}, {first_pair + count}) does not lie in the {f - 1} pairs")
-    if b * count > 65535:
-        raise RuntimeError(f"flowmap_amd: the alignment residuals handle at most 65 535 pairs per call (batch x pairs = {b * count}): split the window")
     if indices is not None:
         indices = indices.contiguous()
         points, maps = indices.numel(), (b, count, indices.numel())
@@ -831,23 +841,11 @@ def focal_sweep(depth, weights, weight_sens, bwd_flow, indices, focal_lengths, c
     dev = check_device(depth, weights, bwd_flow, indices, focal_lengths, candidate_k, candidate_kinv)
     depth, weights, bwd_flow = _f32c(depth, "depth"), _f32c(weights, "correspondence weights"), _f32c(bwd_flow, "backward flow")
     focal_lengths, candidate_k, candidate_kinv = _f32c(focal_lengths, "focal length candidates"), _f32c(candidate_k, "candidate intrinsics"), _f32c(candidate_kinv, "inverse candidate intrinsics")
-    if depth.dim() != 4:
-        raise RuntimeError("flowmap_amd: depth must be (batch, frame, height, width)")
-    b, f, h, w = depth.shape
-    if tuple(bwd_flow.shape) != (b, f - 1, h, w, 2):
-        raise RuntimeError(f"flowmap_amd: flow shape {tuple(bwd_flow.shape)} does not match depth {(b, f, h, w)}")
-    if tuple(weights.shape) != (b, f - 1, h, w):
-        raise RuntimeError(f"flowmap_amd: weight shape {tuple(weights.shape)} does not match depth {(b, f, h, w)}")
+    b, f, h, w = _check_pair_call("the focal sweep", False, depth, None, bwd_flow, weights, first_pair, count)
     n = focal_lengths.numel()
     if focal_lengths.dim() != 1 or n < 1 or tuple(candidate_k.shape) != (n, 3, 3) or tuple(candidate_kinv.shape) != (n, 3, 3):
         raise RuntimeError(f"flowmap_amd: the focal sweep takes candidates (n), K (n, 3, 3) and K^-1 (n, 3, 3); got {tuple(focal_lengths.shape)}, "
                            f"{tuple(candidate_k.shape)}, {tuple(candidate_kinv.shape)}")
-    if h * w >= 1 << 30:
-        raise RuntimeError(f"flowmap_amd: the focal sweep indexes pixels inside a frame with 32 bits: height x width = {h * w} must stay below 2^30")
-    if first_pair < 0 or count < 1 or first_pair + count > f - 1:
-        raise RuntimeError(f"flowmap_amd: the pair window [{first_pair}, {first_pair + count}) does not lie in the {f - 1} pairs")
-    if b * count > 65535:
-        raise RuntimeError(f"flowmap_amd: the focal sweep handles at most 65 535 pairs per call (batch x pairs = {b * count}): split the window")
     indices = indices.contiguous()
     p = indices.numel()
     if indices.dtype != torch.int64 or indices.dim() != 1 or not 1 <= p < 1 << 30:

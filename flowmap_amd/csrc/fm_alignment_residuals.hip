@@ -11,21 +11,22 @@
 // Nothing is staged in LDS; the only LDS is the 64 bytes of the block reduction.  A thread evaluates its four elements before it
 // stores any of them, and depth-sourced it reads their sixteen tap depths together, ahead of corr_load_with (see the kernel).
 //
-// The sums use no atomics.  A thread adds (double)(w·residual) — the fp32 product — and (double)w of its elements in fp64, the wave
-// butterfly and the four wave totals follow in fp64, and thread 0 leaves the workgroup's pair of doubles in its own workspace slot
-// [b][pair][tile] with one 16-byte store.  alignment_residual_sums_kernel then adds a pair's slots in ascending tile order.  Which
-// elements a tile owns depends on the number of elements only — not on the window, not on the batch — so a pair's sums are the same
-// bits however it is reached.
+// The sums use no atomics: a thread adds (double)(w·residual) — the fp32 product — and (double)w of its elements in fp64, and the ordered
+// two-stage sum of fm_ordered_sums.h takes them from there — the workgroup's slot is [b][pair][tile], a row a (batch entry, pair).  Which
+// elements a tile owns depends on the number of elements only, so a pair's sums are the same bits however it is reached.
 #include <hip/hip_runtime.h>
 
 #include "../../include/flowmap_hip.h"
 #include "fm_device.h"
+#include "fm_ordered_sums.h"
+#include "fm_residual_args.h"
 
 namespace fm {
 
 constexpr int kAlignThreads = 256;
 constexpr int kAlignPer = 4;                             // consecutive elements per thread
 constexpr int kAlignTile = kAlignThreads * kAlignPer;    // elements per workgroup
+static_assert(kAlignTile == kAlignResTile, "fm_residual_args.h sizes the workspace");
 
 struct AlignParams {
   const float* depth;      // (B,F,H,W)     [depth-sourced]
@@ -142,50 +143,7 @@ __global__ void __launch_bounds__(kAlignThreads) alignment_residuals_kernel(Alig
   }
 
   if (!sums) return;  // (uniform)
-  __shared__ double red[kAlignThreads / kWave][2];
-  sum_r = wave_sum(sum_r);
-  sum_w = wave_sum(sum_w);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    red[wave][0] = sum_r;
-    red[wave][1] = sum_w;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double2 tot = make_double2(0.0, 0.0);
-    for (int v = 0; v < kAlignThreads / kWave; ++v) {
-      tot.x += red[v][0];
-      tot.y += red[v][1];
-    }
-    // the slot [b][pair][tile] is this workgroup's own: a plain 16-byte store, no atomics
-    reinterpret_cast<double2*>(p.work)[(size_t)bp * p.tiles + blockIdx.x] = tot;
-  }
-}
-
-// One workgroup of 64 threads per (batch entry, pair): the lanes fetch 64 slots at a time, lane 0 adds them in ascending tile order
-// (the order IS the contract: the sums do not depend on how the first launch was scheduled).
-__global__ void __launch_bounds__(kWave) alignment_residual_sums_kernel(const double* __restrict__ work, int tiles, double* __restrict__ pair_sum,
-                                                                       double* __restrict__ pair_weight) {
-  __shared__ double2 slots[kWave];
-  const double2* mine = reinterpret_cast<const double2*>(work) + (size_t)blockIdx.x * tiles;
-  double r = 0.0, w = 0.0;
-  for (int base = 0; base < tiles; base += kWave) {
-    const int i = base + threadIdx.x;
-    if (i < tiles) slots[threadIdx.x] = mine[i];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int have = min(kWave, tiles - base);
-      for (int j = 0; j < have; ++j) {
-        r += slots[j].x;
-        w += slots[j].y;
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    pair_sum[blockIdx.x] = r;
-    pair_weight[blockIdx.x] = w;
-  }
+  block_sum_to_slot<kAlignThreads>(sum_r, sum_w, p.work + 2 * ((size_t)bp * p.tiles + blockIdx.x));
 }
 
 }  // namespace fm
@@ -195,8 +153,8 @@ using namespace fm;
 extern "C" {
 
 int fm_alignment_residual_workspace(long points, long* doubles) {
-  FM_CHECK_ARG(doubles && points >= 1 && points < (1L << 30));
-  doubles[0] = 2 * ((points + kAlignTile - 1) / kAlignTile);
+  FM_CHECK_ARG(alignment_residual_workspace_args_ok(points, doubles));
+  doubles[0] = 2 * alignment_residual_tiles(points);
   return FM_OK;
 }
 
@@ -204,25 +162,21 @@ int fm_alignment_residuals(const float* depth, const float* kinv, const float* s
                            float weight_sensitivity, const float* rel, const int64_t* indices, long points, int batch, int frames,
                            int height, int width, int first_pair, int count, float* residual, float* offset, float* weight_out,
                            double* pair_sum, double* pair_weight, double* workspace, void* stream) {
-  FM_CHECK_ARG(bwd_flow && rel && residual);
-  FM_CHECK_ARG((depth != nullptr) != (surfaces != nullptr) && (depth == nullptr || kinv != nullptr));
+  FM_CHECK_ARG(alignment_residuals_args_ok(depth, kinv, surfaces, bwd_flow, rel, indices, points, batch, frames, height, width, first_pair, count, residual,
+                                           pair_sum, pair_weight, workspace));
   const bool sums = pair_sum != nullptr;
-  FM_CHECK_ARG((pair_weight != nullptr) == sums && (workspace != nullptr) == sums);
-  FM_CHECK_ARG(batch >= 1 && frames >= 2 && height >= 1 && width >= 1 && (long)height * width < (1L << 30));
-  FM_CHECK_ARG(points >= 1 && points < (1L << 30) && (indices != nullptr || points == (long)height * width));
-  FM_CHECK_ARG(first_pair >= 0 && count >= 1 && (long)first_pair + count <= frames - 1 && (long)batch * count <= 65535);
   FM_CHECK_ARG(!sums || (reinterpret_cast<uintptr_t>(workspace) & 15) == 0);
   AlignParams p{depth, kinv, surfaces, bwd_flow, weights, rel, indices, residual, offset, weight_out, sums ? workspace : nullptr};
   p.points = points;
   p.frames = frames, p.height = height, p.width = width, p.first_pair = first_pair, p.count = count;
-  p.tiles = (int)((points + kAlignTile - 1) / kAlignTile);
+  p.tiles = (int)alignment_residual_tiles(points);
   p.weight_sens = weight_sensitivity;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)p.tiles, (unsigned)(batch * count));
   if (depth) hipLaunchKernelGGL((alignment_residuals_kernel<ALIGN_DEPTH>), grid, dim3(kAlignThreads), 0, st, p);
   else hipLaunchKernelGGL((alignment_residuals_kernel<ALIGN_SURF>), grid, dim3(kAlignThreads), 0, st, p);
   if (sums)
-    hipLaunchKernelGGL(alignment_residual_sums_kernel, dim3((unsigned)(batch * count)), dim3(kWave), 0, st, workspace, p.tiles, pair_sum, pair_weight);
+    hipLaunchKernelGGL(ordered_slot_sums_kernel, dim3((unsigned)(batch * count)), dim3(kWave), 0, st, workspace, p.tiles, pair_sum, pair_weight);
   FM_LAUNCH_STATUS();
 }
 

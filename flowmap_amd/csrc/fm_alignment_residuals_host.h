@@ -9,12 +9,13 @@
 #include <cstddef>
 
 #include "../../include/flowmap_hip.h"
+#include "fm_residual_args.h"
 
 extern "C" {
 
 int fm_alignment_residual_workspace(long points, long* doubles) {
-  if (!doubles || points < 1 || points >= (1L << 30)) return 1;
-  doubles[0] = 2 * ((points + 1023) / 1024);
+  if (!fm::alignment_residual_workspace_args_ok(points, doubles)) return 1;
+  doubles[0] = 2 * fm::alignment_residual_tiles(points);
   return 0;
 }
 
@@ -23,13 +24,10 @@ int fm_alignment_residuals(const float* depth, const float* kinv, const float* s
                            int height, int width, int first_pair, int count, float* residual, float* offset, float* weight_out,
                            double* pair_sum, double* pair_weight, double* workspace, void*) {
   using namespace fm;
-  if (!bwd_flow || !rel || !residual) return 1;
-  if ((depth != nullptr) == (surfaces != nullptr) || (depth != nullptr && kinv == nullptr)) return 1;
+  if (!alignment_residuals_args_ok(depth, kinv, surfaces, bwd_flow, rel, indices, points, batch, frames, height, width, first_pair, count, residual, pair_sum,
+                                   pair_weight, workspace))
+    return 1;
   const bool sums = pair_sum != nullptr;
-  if ((pair_weight != nullptr) != sums || (workspace != nullptr) != sums) return 1;
-  if (batch < 1 || frames < 2 || height < 1 || width < 1 || (long)height * width >= (1L << 30)) return 1;
-  if (points < 1 || points >= (1L << 30) || (indices == nullptr && points != (long)height * width)) return 1;
-  if (first_pair < 0 || count < 1 || (long)first_pair + count > frames - 1 || (long)batch * count > 65535) return 1;
   const int n = height * width;
   for (int b = 0; b < batch; ++b)
     for (int lp = 0; lp < count; ++lp) {

@@ -8,21 +8,22 @@
 // flow_term_fast, the fused pass's own term) — a few dozen VALU instructions per pixel, far below the memory time.  Nothing is
 // staged in LDS; the only LDS is the 64 bytes of the block reduction.
 //
-// The sums use no atomics.  A thread adds (double)(residual·mask) and (double)mask of its pixels in fp64, the wave butterfly and
-// the four wave totals follow in fp64, and thread 0 leaves the workgroup's pair of doubles in its own workspace slot
-// [b][pair][direction][workgroup] with one 16-byte store.  flow_residual_sums_kernel then adds a pair's slots in ascending
-// workgroup order.  Which pixels a workgroup owns depends on (height, width) only — not on the window, not on the batch — so a
-// pair's sums are the same bits however it is reached.
+// The sums use no atomics: a thread adds (double)(residual·mask) and (double)mask of its pixels in fp64, and the ordered two-stage sum of
+// fm_ordered_sums.h takes them from there — the workgroup's slot is [b][pair][direction][workgroup], a row a (batch entry, pair,
+// direction).  Which pixels a workgroup owns depends on (height, width) only, so a pair's sums are the same bits however it is reached.
 #include <hip/hip_runtime.h>
 
 #include "../../include/flowmap_hip.h"
 #include "fm_device.h"
+#include "fm_ordered_sums.h"
+#include "fm_residual_args.h"
 
 namespace fm {
 
 constexpr int kResThreads = 256;
 constexpr int kResQuads = 2;                            // quads per thread
 constexpr int kResTile = kResThreads * kResQuads * 4;   // pixels per workgroup
+static_assert(kResTile == kFlowResTile, "fm_residual_args.h sizes the workspace");
 
 struct ResidualParams {
   const float* depth;
@@ -145,50 +146,7 @@ __global__ void __launch_bounds__(kResThreads) flow_residuals_kernel(ResidualPar
   }
 
   if (!sums) return;  // (uniform)
-  __shared__ double red[kResThreads / kWave][2];
-  sum_r = wave_sum(sum_r);
-  sum_m = wave_sum(sum_m);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    red[wave][0] = sum_r;
-    red[wave][1] = sum_m;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double2 tot = make_double2(0.0, 0.0);
-    for (int w = 0; w < kResThreads / kWave; ++w) {
-      tot.x += red[w][0];
-      tot.y += red[w][1];
-    }
-    // the slot [b][pair][direction][workgroup] is this workgroup's own: a plain 16-byte store, no atomics
-    reinterpret_cast<double2*>(p.work)[((size_t)bp * 2 + dir) * p.blocks + blockIdx.x] = tot;
-  }
-}
-
-// One workgroup of 64 threads per (batch entry, pair, direction): the lanes fetch 64 slots at a time, lane 0 adds them in ascending
-// workgroup order (the order IS the contract: the sums do not depend on how the first launch was scheduled).
-__global__ void __launch_bounds__(kWave) flow_residual_sums_kernel(const double* __restrict__ work, int blocks, double* __restrict__ pair_sum,
-                                                                  double* __restrict__ pair_valid) {
-  __shared__ double2 slots[kWave];
-  const double2* mine = reinterpret_cast<const double2*>(work) + (size_t)blockIdx.x * blocks;
-  double s = 0.0, v = 0.0;
-  for (int base = 0; base < blocks; base += kWave) {
-    const int i = base + threadIdx.x;
-    if (i < blocks) slots[threadIdx.x] = mine[i];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int have = min(kWave, blocks - base);
-      for (int j = 0; j < have; ++j) {
-        s += slots[j].x;
-        v += slots[j].y;
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    pair_sum[blockIdx.x] = s;
-    pair_valid[blockIdx.x] = v;
-  }
+  block_sum_to_slot<kResThreads>(sum_r, sum_m, p.work + 2 * (((size_t)bp * 2 + dir) * p.blocks + blockIdx.x));
 }
 
 }  // namespace fm
@@ -198,8 +156,8 @@ using namespace fm;
 extern "C" {
 
 int fm_flow_residual_blocks(int height, int width, int* blocks) {
-  FM_CHECK_ARG(blocks && height >= 1 && width >= 1 && (long)height * width < (1L << 30));
-  blocks[0] = (int)(((long)height * width + kResTile - 1) / kResTile);
+  FM_CHECK_ARG(flow_residual_blocks_args_ok(height, width, blocks));
+  blocks[0] = (int)flow_residual_blocks((long)height * width);
   return FM_OK;
 }
 
@@ -208,29 +166,15 @@ int fm_flow_residuals(const float* depth, const float* k, const float* kinv, con
                       int mapping_kind, float delta, float aspect_x, float aspect_y, int first_pair, int count, float* residual_fwd,
                       float* residual_bwd, float* pred_fwd, float* pred_bwd, double* pair_sum, double* pair_valid, double* workspace,
                       const fm_layout* layouts, void* stream) {
-  FM_CHECK_ARG(depth && k && kinv && t_fwd && t_bwd && flow_fwd && flow_bwd && residual_fwd && residual_bwd);
-  FM_CHECK_ARG((pred_fwd == nullptr) == (pred_bwd == nullptr));
+  FM_CHECK_ARG(flow_residuals_args_ok(depth, k, kinv, t_fwd, t_bwd, flow_fwd, flow_bwd, mask_fwd, mask_bwd, batch, frames, height, width, mapping_kind,
+                                      aspect_x, aspect_y, first_pair, count, residual_fwd, residual_bwd, pred_fwd, pred_bwd, pair_sum, pair_valid, workspace));
   const bool sums = pair_sum != nullptr;
-  FM_CHECK_ARG((pair_valid != nullptr) == sums && (workspace != nullptr) == sums && (!sums || (mask_fwd && mask_bwd)));
-  FM_CHECK_ARG(batch >= 1 && frames >= 2 && height >= 1 && width >= 1 && (long)height * width < (1L << 30));
-  FM_CHECK_ARG(mapping_kind >= 0 && mapping_kind <= 2);
-  FM_CHECK_ARG(first_pair >= 0 && count >= 1 && (long)first_pair + count <= frames - 1 && (long)batch * count <= 65535);
-  FM_CHECK_ARG(aspect_x > 0.f && aspect_y > 0.f);
   ResidualParams p{depth, k, kinv, t_fwd, t_bwd, flow_fwd, flow_bwd, sums ? mask_fwd : nullptr, sums ? mask_bwd : nullptr, residual_fwd, residual_bwd,
                    pred_fwd, pred_bwd, workspace};
   const long n = (long)height * width;
-  {  // element strides of the five image stacks (dense unless the caller described a view)
-    const long per_frame[5] = {n, 2 * n, 2 * n, n, n};
-    const long frames_of[5] = {frames, frames - 1, frames - 1, frames - 1, frames - 1};
-    for (int i = 0; i < 5; ++i) {
-      const bool given = layouts && (layouts[i].frame_stride != 0 || layouts[i].batch_stride != 0);
-      p.fs[i] = given ? layouts[i].frame_stride : per_frame[i];
-      p.bs[i] = given ? layouts[i].batch_stride : per_frame[i] * frames_of[i];
-      FM_CHECK_ARG(p.fs[i] >= per_frame[i] && (batch == 1 || p.bs[i] >= p.fs[i] * (frames_of[i] - 1) + per_frame[i]));
-    }
-  }
+  FM_CHECK_ARG(flow_residual_strides(layouts, batch, frames, n, p.fs, p.bs));
   p.frames = frames, p.height = height, p.width = width, p.first_pair = first_pair, p.count = count;
-  p.blocks = (int)((n + kResTile - 1) / kResTile);
+  p.blocks = (int)flow_residual_blocks(n);
   p.delta = delta, p.ax = aspect_x, p.ay = aspect_y;
   auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   bool vec4 = width % 4 == 0 && aligned(depth) && aligned(flow_fwd) && aligned(flow_bwd) && aligned(residual_fwd) && aligned(residual_bwd);
@@ -249,7 +193,7 @@ int fm_flow_residuals(const float* depth, const float* k, const float* kinv, con
   else FM_RES_LAUNCH(1);
 #undef FM_RES_LAUNCH
   if (sums)
-    hipLaunchKernelGGL(flow_residual_sums_kernel, dim3((unsigned)(batch * count * 2)), dim3(kWave), 0, st, workspace, p.blocks, pair_sum, pair_valid);
+    hipLaunchKernelGGL(ordered_slot_sums_kernel, dim3((unsigned)(batch * count * 2)), dim3(kWave), 0, st, workspace, p.blocks, pair_sum, pair_valid);
   FM_LAUNCH_STATUS();
 }
 

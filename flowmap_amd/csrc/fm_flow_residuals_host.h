@@ -9,6 +9,7 @@
 #include <cstddef>
 
 #include "../../include/flowmap_hip.h"
+#include "fm_residual_args.h"
 
 namespace fm {
 namespace residuals_host {
@@ -71,8 +72,8 @@ inline void run(const float* depth, const float* k, const float* kinv, const flo
 extern "C" {
 
 int fm_flow_residual_blocks(int height, int width, int* blocks) {
-  if (!blocks || height < 1 || width < 1) return 1;
-  blocks[0] = (int)(((long)height * width + 2047) / 2048);
+  if (!fm::flow_residual_blocks_args_ok(height, width, blocks)) return 1;
+  blocks[0] = (int)fm::flow_residual_blocks((long)height * width);
   return 0;
 }
 
@@ -81,22 +82,12 @@ int fm_flow_residuals(const float* depth, const float* k, const float* kinv, con
                       int mapping_kind, float delta, float aspect_x, float aspect_y, int first_pair, int count, float* residual_fwd,
                       float* residual_bwd, float* pred_fwd, float* pred_bwd, double* pair_sum, double* pair_valid, double* workspace,
                       const fm_layout* layouts, void*) {
-  if (!depth || !k || !kinv || !t_fwd || !t_bwd || !flow_fwd || !flow_bwd || !residual_fwd || !residual_bwd) return 1;
-  if ((pred_fwd == nullptr) != (pred_bwd == nullptr)) return 1;
+  if (!fm::flow_residuals_args_ok(depth, k, kinv, t_fwd, t_bwd, flow_fwd, flow_bwd, mask_fwd, mask_bwd, batch, frames, height, width, mapping_kind, aspect_x,
+                                  aspect_y, first_pair, count, residual_fwd, residual_bwd, pred_fwd, pred_bwd, pair_sum, pair_valid, workspace))
+    return 1;
   const bool sums = pair_sum != nullptr;
-  if ((pair_valid != nullptr) != sums || (workspace != nullptr) != sums || (sums && (!mask_fwd || !mask_bwd))) return 1;
-  if (batch < 1 || frames < 2 || height < 1 || width < 1 || mapping_kind < 0 || mapping_kind > 2) return 1;
-  if (first_pair < 0 || count < 1 || (long)first_pair + count > frames - 1 || !(aspect_x > 0.f) || !(aspect_y > 0.f)) return 1;
-  const long n = (long)height * width;
-  const long per_frame[5] = {n, 2 * n, 2 * n, n, n};
-  const long frames_of[5] = {frames, frames - 1, frames - 1, frames - 1, frames - 1};
   long fs[5], bs[5];
-  for (int i = 0; i < 5; ++i) {
-    const bool given = layouts && (layouts[i].frame_stride != 0 || layouts[i].batch_stride != 0);
-    fs[i] = given ? layouts[i].frame_stride : per_frame[i];
-    bs[i] = given ? layouts[i].batch_stride : per_frame[i] * frames_of[i];
-    if (fs[i] < per_frame[i] || (batch > 1 && bs[i] < fs[i] * (frames_of[i] - 1) + per_frame[i])) return 1;
-  }
+  if (!fm::flow_residual_strides(layouts, batch, frames, (long)height * width, fs, bs)) return 1;
   const float* const flow[2] = {flow_fwd, flow_bwd};
   const float* const mask[2] = {sums ? mask_fwd : nullptr, sums ? mask_bwd : nullptr};
   float* const res[2] = {residual_fwd, residual_bwd};

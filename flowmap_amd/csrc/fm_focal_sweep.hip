@@ -21,6 +21,7 @@
 #include "../../include/flowmap_hip.h"
 #include "fm_device.h"
 #include "fm_pose.h"
+#include "fm_residual_args.h"
 
 namespace fm {
 
@@ -174,11 +175,8 @@ int fm_focal_sweep(const float* depth, const float* weights, float weight_sensit
                    const float* focal_lengths, const float* candidate_k, const float* candidate_kinv, int batch, int frames, int height, int width,
                    int first_pair, int count, int candidates, double* error, float* soft, float* focal, float* intrinsics, float* poses,
                    float* point_error, void* stream) {
-  FM_CHECK_ARG(depth && weights && bwd_flow && indices && focal_lengths && candidate_k && candidate_kinv);
-  FM_CHECK_ARG(error && soft && focal && intrinsics);
-  FM_CHECK_ARG(batch >= 1 && frames >= 2 && height >= 1 && width >= 1 && (long)height * width < (1L << 30));
-  FM_CHECK_ARG(points >= 1 && points < (1L << 30) && candidates >= 1);
-  FM_CHECK_ARG(first_pair >= 0 && count >= 1 && (long)first_pair + count <= frames - 1 && (long)batch * count <= 65535);
+  FM_CHECK_ARG(focal_sweep_args_ok(depth, weights, bwd_flow, indices, points, focal_lengths, candidate_k, candidate_kinv, batch, frames, height, width,
+                                   first_pair, count, candidates, error, soft, focal, intrinsics));
   SweepParams p{depth, weights, bwd_flow, indices, candidate_k, candidate_kinv, error, poses, point_error};
   p.points = points;
   p.frames = frames, p.height = height, p.width = width, p.first_pair = first_pair, p.count = count, p.candidates = candidates;

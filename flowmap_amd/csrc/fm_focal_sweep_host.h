@@ -13,6 +13,7 @@
 #include <cstddef>
 
 #include "../../include/flowmap_hip.h"
+#include "fm_residual_args.h"
 
 namespace fm {
 inline void pose_solve_one(const double* st, float* tb, float* tf, double* ax);
@@ -25,11 +26,9 @@ int fm_focal_sweep(const float* depth, const float* weights, float weight_sensit
                    int first_pair, int count, int candidates, double* error, float* soft, float* focal, float* intrinsics, float* poses,
                    float* point_error, void*) {
   using namespace fm;
-  if (!depth || !weights || !bwd_flow || !indices || !focal_lengths || !candidate_k || !candidate_kinv) return 1;
-  if (!error || !soft || !focal || !intrinsics) return 1;
-  if (batch < 1 || frames < 2 || height < 1 || width < 1 || (long)height * width >= (1L << 30)) return 1;
-  if (points < 1 || points >= (1L << 30) || candidates < 1) return 1;
-  if (first_pair < 0 || count < 1 || (long)first_pair + count > frames - 1 || (long)batch * count > 65535) return 1;
+  if (!focal_sweep_args_ok(depth, weights, bwd_flow, indices, points, focal_lengths, candidate_k, candidate_kinv, batch, frames, height, width, first_pair,
+                           count, candidates, error, soft, focal, intrinsics))
+    return 1;
   const int n = height * width;
   for (int b = 0; b < batch; ++b)
     for (int lp = 0; lp < count; ++lp) {

@@ -1,0 +1,109 @@
+// Argument checks and size formulas of the residual entry points (include/flowmap_hip.h: fm_flow_residuals, fm_track_residuals,
+// fm_alignment_residuals, fm_focal_sweep and their size functions), stated ONCE: the device build (fm_*.hip) and the serial host build of
+// the same ABI (fm_*_host.h) both call these, so the two refuse the same calls and size the same workspaces.  Plain C++, no HIP.
+// Device-only, and therefore not here: the 16-byte path's eligibility and the pointer alignment the kernels need (the host build reads
+// element by element and never touches the workspace).
+#pragma once
+
+#include <stdint.h>
+
+#include "../../include/flowmap_hip.h"
+
+namespace fm {
+
+constexpr int kFlowResTile = 2048;    // pixels per workgroup of flow_residuals_kernel
+constexpr int kAlignResTile = 1024;   // elements per workgroup of alignment_residuals_kernel
+constexpr int kTrackResChunk = 64;    // points per wave of track_residuals_kernel: one workspace slot per (fs, ft, chunk)
+constexpr int kTrackResThreads = 256;
+constexpr long kResMaxPixels = 1L << 30;  // pixels of a frame are indexed with 32 bits
+constexpr long kResMaxRows = 65535;       // (batch entry, pair) rows of one call: a grid dimension
+
+static inline bool res_frame_ok(int height, int width) { return height >= 1 && width >= 1 && (long)height * width < kResMaxPixels; }
+static inline bool res_window_ok(int batch, int frames, int first_pair, int count) {
+  return batch >= 1 && frames >= 2 && first_pair >= 0 && count >= 1 && (long)first_pair + count <= frames - 1 && (long)batch * count <= kResMaxRows;
+}
+
+// ---- flow ----
+static inline long flow_residual_blocks(long pixels) { return (pixels + kFlowResTile - 1) / kFlowResTile; }
+static inline bool flow_residual_blocks_args_ok(int height, int width, const int* blocks) { return blocks && res_frame_ok(height, width); }
+
+static inline bool flow_residuals_args_ok(const float* depth, const float* k, const float* kinv, const float* t_fwd, const float* t_bwd,
+                                          const float* flow_fwd, const float* flow_bwd, const float* mask_fwd, const float* mask_bwd, int batch, int frames,
+                                          int height, int width, int mapping_kind, float aspect_x, float aspect_y, int first_pair, int count,
+                                          const float* residual_fwd, const float* residual_bwd, const float* pred_fwd, const float* pred_bwd,
+                                          const double* pair_sum, const double* pair_valid, const double* workspace) {
+  if (!(depth && k && kinv && t_fwd && t_bwd && flow_fwd && flow_bwd && residual_fwd && residual_bwd)) return false;
+  if ((pred_fwd == nullptr) != (pred_bwd == nullptr)) return false;
+  const bool sums = pair_sum != nullptr;
+  if ((pair_valid != nullptr) != sums || (workspace != nullptr) != sums || (sums && !(mask_fwd && mask_bwd))) return false;
+  if (!res_frame_ok(height, width) || !res_window_ok(batch, frames, first_pair, count)) return false;
+  return mapping_kind >= 0 && mapping_kind <= 2 && aspect_x > 0.f && aspect_y > 0.f;
+}
+
+// Element strides of depth, flow_fwd, flow_bwd, mask_fwd, mask_bwd (dense unless the caller described a view); false: a stack's frames or
+// batch entries would overlap.
+static inline bool flow_residual_strides(const fm_layout* layouts, int batch, int frames, long pixels, long fs[5], long bs[5]) {
+  const long per_frame[5] = {pixels, 2 * pixels, 2 * pixels, pixels, pixels};
+  const long frames_of[5] = {frames, frames - 1, frames - 1, frames - 1, frames - 1};
+  for (int i = 0; i < 5; ++i) {
+    const bool given = layouts && (layouts[i].frame_stride != 0 || layouts[i].batch_stride != 0);
+    fs[i] = given ? layouts[i].frame_stride : per_frame[i];
+    bs[i] = given ? layouts[i].batch_stride : per_frame[i] * frames_of[i];
+    if (fs[i] < per_frame[i] || (batch != 1 && bs[i] < fs[i] * (frames_of[i] - 1) + per_frame[i])) return false;
+  }
+  return true;
+}
+
+// ---- tracking ----
+// (constexpr: the kernels call these two as well)
+constexpr long track_res_chunks(long p) { return (p + kTrackResChunk - 1) / kTrackResChunk; }
+// doubles of workspace of one segment: [f][f][chunks][2] pair partials, then [f][p][2] per-source-frame track partials
+constexpr long track_res_work(long f, long p) { return 2 * (f * f * track_res_chunks(p) + f * p); }
+static inline bool track_residual_workspace_args_ok(int frames, int points, const long* doubles) { return doubles && frames >= 1 && points >= 1; }
+static inline long track_res_point_blocks(int pmax) { return ((long)pmax + kTrackResThreads - 1) / kTrackResThreads; }
+static inline long track_res_sum_blocks(int pmax, int fmax) {
+  const long pair_blocks = ((long)fmax * fmax + kTrackResThreads - 1) / kTrackResThreads, point_blocks = track_res_point_blocks(pmax);
+  return pair_blocks > point_blocks ? pair_blocks : point_blocks;
+}
+
+static inline bool track_residuals_args_ok(const float* depth, const float* kinv, const float* ext, const float* ext_inv, const float* k, int frames,
+                                           const float* xy, const uint8_t* vis, const int32_t* seg, int first_segment, int count, int pmax, int fmax,
+                                           int height, int width, int mapping_kind, float aspect_x, float aspect_y, const float* tgt, const float* residual,
+                                           const uint8_t* visible, const double* pair_sum, const double* pair_count, const double* track_sum,
+                                           const double* track_count, const double* workspace) {
+  if (!(depth && kinv && ext && ext_inv && k && xy && vis && seg && tgt && residual && visible)) return false;
+  const bool sums = pair_sum != nullptr;
+  if ((pair_count != nullptr) != sums || (track_sum != nullptr) != sums || (track_count != nullptr) != sums || (workspace != nullptr) != sums) return false;
+  if (!(frames >= 1 && first_segment >= 0 && count >= 1 && pmax >= 1 && fmax >= 1 && res_frame_ok(height, width))) return false;
+  if (!(mapping_kind >= 0 && mapping_kind <= 2 && aspect_x > 0.f && aspect_y > 0.f)) return false;
+  return (long)count * fmax < (1L << 31) - 1 && track_res_point_blocks(pmax) <= kResMaxRows && track_res_sum_blocks(pmax, fmax) <= kResMaxRows;
+}
+
+// ---- alignment ----
+static inline long alignment_residual_tiles(long points) { return (points + kAlignResTile - 1) / kAlignResTile; }
+static inline bool res_points_ok(long points) { return points >= 1 && points < kResMaxPixels; }
+static inline bool alignment_residual_workspace_args_ok(long points, const long* doubles) { return doubles && res_points_ok(points); }
+
+static inline bool alignment_residuals_args_ok(const float* depth, const float* kinv, const float* surfaces, const float* bwd_flow, const float* rel,
+                                               const int64_t* indices, long points, int batch, int frames, int height, int width, int first_pair, int count,
+                                               const float* residual, const double* pair_sum, const double* pair_weight, const double* workspace) {
+  if (!(bwd_flow && rel && residual)) return false;
+  if ((depth != nullptr) == (surfaces != nullptr) || (depth != nullptr && kinv == nullptr)) return false;
+  const bool sums = pair_sum != nullptr;
+  if ((pair_weight != nullptr) != sums || (workspace != nullptr) != sums) return false;
+  if (!res_frame_ok(height, width) || !res_window_ok(batch, frames, first_pair, count)) return false;
+  return res_points_ok(points) && (indices != nullptr || points == (long)height * width);
+}
+
+// ---- focal sweep ----
+static inline bool focal_sweep_args_ok(const float* depth, const float* weights, const float* bwd_flow, const int64_t* indices, long points,
+                                       const float* focal_lengths, const float* candidate_k, const float* candidate_kinv, int batch, int frames, int height,
+                                       int width, int first_pair, int count, int candidates, const double* error, const float* soft, const float* focal,
+                                       const float* intrinsics) {
+  if (!(depth && weights && bwd_flow && indices && focal_lengths && candidate_k && candidate_kinv)) return false;
+  if (!(error && soft && focal && intrinsics)) return false;
+  if (!res_frame_ok(height, width) || !res_window_ok(batch, frames, first_pair, count)) return false;
+  return res_points_ok(points) && candidates >= 1;
+}
+
+}  // namespace fm

@@ -18,15 +18,15 @@
 // on the segment alone — not on the window, not on the other segments — so a segment's sums are the same bits however it is reached.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "../../include/flowmap_hip.h"
 #include "fm_device.h"
 #include "fm_pose.h"
+#include "fm_residual_args.h"
 
 namespace fm {
 
-constexpr int kTrResThreads = 256;
+constexpr int kTrResThreads = kTrackResThreads;
+static_assert(kTrackResChunk == kWave, "a workspace slot per wave (fm_residual_args.h: track_res_chunks, track_res_work)");
 
 struct TrackResParams {
   const float* depth;
@@ -49,10 +49,6 @@ struct TrackResParams {
   int frames, first, count, fmax, height, width;
   float delta, ax, ay;
 };
-
-__host__ __device__ constexpr long track_res_chunks(long p) { return (p + kWave - 1) / kWave; }
-// doubles of workspace of one segment: [f][f][chunks][2] pair partials, then [f][p][2] per-source-frame track partials
-__host__ __device__ constexpr long track_res_work(long f, long p) { return 2 * (f * f * track_res_chunks(p) + f * p); }
 
 // Where segment sg's share of every output starts: the segments of the window lie one after the other.
 struct SegPlace {
@@ -172,7 +168,7 @@ using namespace fm;
 extern "C" {
 
 int fm_track_residual_workspace(int frames, int points, long* doubles) {
-  FM_CHECK_ARG(doubles && frames >= 1 && points >= 1);
+  FM_CHECK_ARG(track_residual_workspace_args_ok(frames, points, doubles));
   doubles[0] = track_res_work(frames, points);
   return FM_OK;
 }
@@ -182,14 +178,10 @@ int fm_track_residuals(const float* depth, const float* kinv, const float* ext, 
                        int mapping_kind, float delta, float aspect_x, float aspect_y, float* tgt, float* residual, uint8_t* visible,
                        float* xy_target, double* pair_sum, double* pair_count, double* track_sum, double* track_count, double* workspace,
                        void* stream) {
-  FM_CHECK_ARG(depth && kinv && ext && ext_inv && k && xy && vis && seg && tgt && residual && visible);
+  FM_CHECK_ARG(track_residuals_args_ok(depth, kinv, ext, ext_inv, k, frames, xy, vis, seg, first_segment, count, pmax, fmax, height, width, mapping_kind,
+                                       aspect_x, aspect_y, tgt, residual, visible, pair_sum, pair_count, track_sum, track_count, workspace));
   const bool sums = pair_sum != nullptr;
-  FM_CHECK_ARG((pair_count != nullptr) == sums && (track_sum != nullptr) == sums && (track_count != nullptr) == sums && (workspace != nullptr) == sums);
-  FM_CHECK_ARG(frames >= 1 && first_segment >= 0 && count >= 1 && pmax >= 1 && fmax >= 1 && height >= 1 && width >= 1);
-  FM_CHECK_ARG((long)height * width < (1L << 30) && mapping_kind >= 0 && mapping_kind <= 2 && aspect_x > 0.f && aspect_y > 0.f);
-  const long point_blocks = ((long)pmax + kTrResThreads - 1) / kTrResThreads;
-  const long sum_blocks = std::max(((long)fmax * fmax + kTrResThreads - 1) / kTrResThreads, point_blocks);
-  FM_CHECK_ARG((long)count * fmax < (1L << 31) - 1 && point_blocks <= 65535 && sum_blocks <= 65535);
+  const long point_blocks = track_res_point_blocks(pmax), sum_blocks = track_res_sum_blocks(pmax, fmax);
   FM_CHECK_ARG(!sums || (reinterpret_cast<uintptr_t>(workspace) & 15) == 0);
   FM_CHECK_ARG((reinterpret_cast<uintptr_t>(xy) & 7) == 0 && (!xy_target || (reinterpret_cast<uintptr_t>(xy_target) & 7) == 0));
   TrackResParams a{depth, kinv, ext, ext_inv, k, xy, vis, seg, tgt, residual, visible, xy_target, workspace, pair_sum, pair_count, track_sum, track_count,

@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "../../include/flowmap_hip.h"
+#include "fm_residual_args.h"
 
 namespace fm {
 namespace track_residuals_host {
@@ -73,8 +74,8 @@ inline void run(const float* depth, const float* kinv, const float* ext, const f
 extern "C" {
 
 int fm_track_residual_workspace(int frames, int points, long* doubles) {
-  if (!doubles || frames < 1 || points < 1) return 1;
-  doubles[0] = 2 * ((long)frames * frames * (((long)points + 63) / 64) + (long)frames * points);
+  if (!fm::track_residual_workspace_args_ok(frames, points, doubles)) return 1;
+  doubles[0] = fm::track_res_work(frames, points);
   return 0;
 }
 
@@ -82,11 +83,9 @@ int fm_track_residuals(const float* depth, const float* kinv, const float* ext, 
                        const uint8_t* vis, const int32_t* seg, int first_segment, int count, int pmax, int fmax, int height, int width,
                        int mapping_kind, float delta, float aspect_x, float aspect_y, float* tgt, float* residual, uint8_t* visible,
                        float* xy_target, double* pair_sum, double* pair_count, double* track_sum, double* track_count, double* workspace, void*) {
-  if (!depth || !kinv || !ext || !ext_inv || !k || !xy || !vis || !seg || !tgt || !residual || !visible) return 1;
-  const bool sums = pair_sum != nullptr;
-  if ((pair_count != nullptr) != sums || (track_sum != nullptr) != sums || (track_count != nullptr) != sums || (workspace != nullptr) != sums) return 1;
-  if (frames < 1 || first_segment < 0 || count < 1 || pmax < 1 || fmax < 1 || height < 1 || width < 1) return 1;
-  if (mapping_kind < 0 || mapping_kind > 2 || !(aspect_x > 0.f) || !(aspect_y > 0.f)) return 1;
+  if (!fm::track_residuals_args_ok(depth, kinv, ext, ext_inv, k, frames, xy, vis, seg, first_segment, count, pmax, fmax, height, width, mapping_kind, aspect_x,
+                                   aspect_y, tgt, residual, visible, pair_sum, pair_count, track_sum, track_count, workspace))
+    return 1;
   for (int sg = first_segment; sg < first_segment + count; ++sg)
     if (seg[sg * 4] < 0 || seg[sg * 4 + 1] < 1 || seg[sg * 4 + 2] < 1 || seg[sg * 4] + seg[sg * 4 + 1] > frames) return 1;
 #define FM_TRES_HOST(K)                                                                                                                        \

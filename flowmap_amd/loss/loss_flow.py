@@ -9,6 +9,7 @@ import torch
 from torch import Tensor
 
 from .. import _ops, _reference
+from .._base import parse_window
 from ..types import FlowResiduals
 from ..model.projection import LazyExtrinsics, LazySurfaces, _dense_extrinsics, compute_backward_flow, compute_forward_flow, sample_image_grid
 from .loss import Loss, LossCfgCommon, or_one
@@ -117,24 +118,6 @@ class LossFlow(Loss[LossFlowCfg]):
         return loss_sum / or_one(valid_sum)
 
     # -- per-pixel view ---------------------------------------------------------------------
-    @staticmethod
-    def _pair_window(pairs, total: int):
-        """``pairs`` of residuals() -> (first, count): None (all pairs), a slice with step 1, or (first, count)."""
-        if pairs is None:
-            first, count = 0, total
-        elif isinstance(pairs, slice):
-            if pairs.step not in (None, 1):
-                raise ValueError(f"flowmap_amd: LossFlow.residuals takes a slice of pairs with step 1 (got step {pairs.step})")
-            first, stop, _ = pairs.indices(total)
-            count = stop - first
-        elif isinstance(pairs, (tuple, list)) and len(pairs) == 2 and all(isinstance(x, int) and not isinstance(x, bool) for x in pairs):
-            first, count = pairs
-        else:
-            raise ValueError(f"flowmap_amd: LossFlow.residuals: pairs must be None, a slice with step 1 or (first, count), got {pairs!r}")
-        if first < 0 or count < 1 or first + count > total:
-            raise ValueError(f"flowmap_amd: LossFlow.residuals: the pairs [{first}, {first + count}) do not lie in the {total} pairs of the video")
-        return int(first), int(count)
-
     def residuals(self, batch, flows, model_output, pairs=None, predicted_flow: bool = False, sums: bool = True) -> FlowResiduals:
         """The per-pixel and per-pair quantities of ``compute_unweighted_loss`` (loss_flow.py:46-68) for the pairs ``pairs`` — None (all), a
         slice with step 1, or (first, count): ``forward`` / ``backward`` = mapping.forward(xy_flowed − xy, flow, (h, w)) BEFORE the mask;
@@ -146,7 +129,7 @@ class LossFlow(Loss[LossFlowCfg]):
         general-path operators; host tensors after install() go to the reference's own functions.  Never differentiable, and it leaves
         the training step alone: no look-ahead or fused-Adam state, no tap image, no note on the flow tensors."""
         total = model_output.depths.shape[1] - 1
-        first, count = self._pair_window(pairs, total)
+        first, count = parse_window(pairs, total, "LossFlow.residuals", "pairs")
         with torch.no_grad():
             if self._fusable(model_output) and not _reference.on_host(batch):
                 return self._residuals_fused(flows, model_output, first, count, predicted_flow, sums)

@@ -11,6 +11,7 @@ from torch import Tensor
 import torch
 
 from .. import _ops, _reference
+from .._base import parse_window
 from ..types import TrackResiduals
 from ..model.projection import LazySurfaces, _dense_extrinsics, compute_track_flow
 from .loss import Loss, LossCfgCommon, or_one
@@ -107,26 +108,6 @@ class LossTracking(Loss[LossTrackingCfg]):
         return torch.stack(numerators).sum() / or_one(torch.stack(counts).sum())
 
     # -- per-track view ---------------------------------------------------------------------
-    @staticmethod
-    def _segment_window(segments, total: int):
-        """``segments`` of residuals() -> (first, count): None (all segments), an int, a slice with step 1, or (first, count)."""
-        if segments is None:
-            first, count = 0, total
-        elif isinstance(segments, int) and not isinstance(segments, bool):
-            first, count = (segments + total if segments < 0 else segments), 1
-        elif isinstance(segments, slice):
-            if segments.step not in (None, 1):
-                raise ValueError(f"flowmap_amd: LossTracking.residuals takes a slice of segments with step 1 (got step {segments.step})")
-            first, stop, _ = segments.indices(total)
-            count = stop - first
-        elif isinstance(segments, (tuple, list)) and len(segments) == 2 and all(isinstance(x, int) and not isinstance(x, bool) for x in segments):
-            first, count = segments
-        else:
-            raise ValueError(f"flowmap_amd: LossTracking.residuals: segments must be None, an int, a slice with step 1 or (first, count), got {segments!r}")
-        if first < 0 or count < 1 or first + count > total:
-            raise ValueError(f"flowmap_amd: LossTracking.residuals: the segments [{first}, {first + count}) do not lie in the {total} segments of the track list")
-        return int(first), int(count)
-
     def residuals(self, batch, tracks, model_output, segments=None, predicted: bool = False, sums: bool = True) -> list:
         """The per-(source frame, target frame, point) quantities of ``compute_unweighted_loss`` (loss_tracking.py:44-61) for the segments
         ``segments`` of ``tracks`` — None (all), an int, a slice with step 1, or (first, count): one ``TrackResiduals`` per segment, in list
@@ -144,7 +125,7 @@ class LossTracking(Loss[LossTrackingCfg]):
         it leaves the training step alone: no look-ahead or fused-Adam state, no tap plan or tap image, no announcement of track pixels."""
         if tracks is None or len(tracks) == 0:
             raise ValueError("flowmap_amd: LossTracking.residuals: there are no tracks (tracks is None or an empty list)")
-        first, count = self._segment_window(segments, len(tracks))
+        first, count = parse_window(segments, len(tracks), "LossTracking.residuals", "segments", allow_int=True)
         with torch.no_grad():
             if self._fusable(model_output, tracks) and not _reference.on_host(batch):
                 return self._residuals_fused(tracks, model_output, first, count, predicted, sums)

@@ -22,6 +22,7 @@ import torch
 from torch import Tensor
 
 from .. import _ops
+from .._base import parse_window
 from .._lib import check_device, using_test_double
 from ..types import AlignmentResiduals, FocalSweep
 
@@ -539,23 +540,34 @@ def align_surfaces(surfaces, backward_flows: Tensor, backward_weights: Tensor, i
     return _align_surfaces(surfaces, backward_flows, backward_weights, indices, lazy_ok=False)
 
 
-def _alignment_pair_window(pairs, total: int):
-    """``pairs`` of alignment_residuals -> (first, count): None (all pairs), a slice with step 1, or (first, count) — the forms of
-    LossFlow.residuals."""
-    if pairs is None:
-        first, count = 0, total
-    elif isinstance(pairs, slice):
-        if pairs.step not in (None, 1):
-            raise ValueError(f"flowmap_amd: alignment_residuals takes a slice of pairs with step 1 (got step {pairs.step})")
-        first, stop, _ = pairs.indices(total)
-        count = stop - first
-    elif isinstance(pairs, (tuple, list)) and len(pairs) == 2 and all(isinstance(x, int) and not isinstance(x, bool) for x in pairs):
-        first, count = pairs
-    else:
-        raise ValueError(f"flowmap_amd: alignment_residuals: pairs must be None, a slice with step 1 or (first, count), got {pairs!r}")
-    if first < 0 or count < 1 or first + count > total:
-        raise ValueError(f"flowmap_amd: alignment_residuals: the pairs [{first}, {first + count}) do not lie in the {total} pairs of the video")
-    return int(first), int(count)
+# The front door of the two diagnostics below (alignment_residuals, focal_sweep): what they refuse and unwrap alike.
+
+
+def _refuse_host(what: str, dev) -> None:
+    if dev.type != "cuda" and not using_test_double():
+        raise RuntimeError(f"flowmap_amd: {what}: tensors are on {dev}; it runs on the GPU only (device 'cuda' on ROCm) — the reference has no "
+                           "function that returns this quantity, so host tensors have nowhere to go. There is no CPU fallback.")
+
+
+def _check_indices(what: str, indices, dev) -> None:
+    if indices is None:
+        return
+    if not torch.is_tensor(indices) or indices.dtype != torch.int64:
+        raise RuntimeError(f"flowmap_amd: {what}: indices must be an int64 tensor (got {getattr(indices, 'dtype', type(indices).__name__)})")
+    if indices.device != dev:
+        raise RuntimeError(f"flowmap_amd: {what}: indices are on {indices.device}, the depths on {dev}")
+    if indices.dim() != 1 or indices.numel() == 0:
+        raise RuntimeError(f"flowmap_amd: {what}: indices must be a non-empty 1-D tensor (got shape {tuple(indices.shape)})")
+
+
+def _peek_weights(weights):
+    """(what the kernel reads, sensitivity) of a weights argument WITHOUT evaluating a LazyWeights: its logits and sensitivity, or — at
+    sensitivity 0 — its value, not kept on the object; a tensor (or None) as it is, with sensitivity 0."""
+    if not isinstance(weights, LazyWeights):
+        return weights, 0.0
+    if weights.sensitivity != 0.0:
+        return weights.logits, weights.sensitivity
+    return (weights._dense if weights._dense is not None else (0.0 * weights.logits).sigmoid()), 0.0
 
 
 def alignment_residuals(surfaces, backward_flows: Tensor, backward_weights, extrinsics, indices: Optional[Tensor] = None, pairs=None,
@@ -581,9 +593,7 @@ def alignment_residuals(surfaces, backward_flows: Tensor, backward_weights, extr
         if not torch.is_tensor(src) or not torch.is_tensor(backward_flows):
             raise RuntimeError("flowmap_amd: alignment_residuals: surfaces must be a LazySurfaces or a tensor, backward_flows a tensor")
         dev = src.device
-        if dev.type != "cuda" and not using_test_double():
-            raise RuntimeError(f"flowmap_amd: alignment_residuals: tensors are on {dev}; it runs on the GPU only (device 'cuda' on ROCm) — the reference "
-                               "has no function that returns this quantity, so host tensors have nowhere to go. There is no CPU fallback.")
+        _refuse_host("alignment_residuals", dev)
         if (lazy and src.dim() != 4) or (not lazy and (src.dim() != 5 or src.shape[-1] != 3)):
             raise RuntimeError(f"flowmap_amd: alignment_residuals: surfaces of shape {tuple(surfaces.shape)}; expected (batch, frame, height, width, 3)")
         b, f, h, w = src.shape[:4]
@@ -596,14 +606,8 @@ def alignment_residuals(surfaces, backward_flows: Tensor, backward_weights, extr
         if tuple(extrinsics.shape) != (b, f, 4, 4):
             raise RuntimeError(f"flowmap_amd: alignment_residuals: extrinsics of shape {tuple(extrinsics.shape)} do not match the depths {(b, f, h, w)} "
                                f"(a depth tensor that holds fewer frames than the poses — a frame shard — is not supported): expected {(b, f, 4, 4)}")
-        if indices is not None:
-            if not torch.is_tensor(indices) or indices.dtype != torch.int64:
-                raise RuntimeError(f"flowmap_amd: alignment_residuals: indices must be an int64 tensor (got {getattr(indices, 'dtype', type(indices).__name__)})")
-            if indices.device != dev:
-                raise RuntimeError(f"flowmap_amd: alignment_residuals: indices are on {indices.device}, the depths on {dev}")
-            if indices.dim() != 1 or indices.numel() == 0:
-                raise RuntimeError(f"flowmap_amd: alignment_residuals: indices must be a non-empty 1-D tensor (got shape {tuple(indices.shape)})")
-        first, count = _alignment_pair_window(pairs, f - 1)
+        _check_indices("alignment_residuals", indices, dev)
+        first, count = parse_window(pairs, f - 1, "alignment_residuals", "pairs")
 
         # T_i = E_i⁻¹·E_{i+1}: the second of the pair the fit leaves on its extrinsics (rel_inv, rel) and of fm_relative_pose_fwd's outputs
         direct = getattr(extrinsics, "_fm_relative_poses", None)
@@ -615,12 +619,7 @@ def alignment_residuals(surfaces, backward_flows: Tensor, backward_weights, extr
                 ext = ext._dense if ext._dense is not None else _ops.PoseChain.apply(ext._rel.detach())
             rel = _ops.RelativePoses.apply(ext.detach())[1]
 
-        sens = 0.0
-        if isinstance(backward_weights, LazyWeights):
-            if backward_weights.sensitivity != 0.0:
-                backward_weights, sens = backward_weights.logits, backward_weights.sensitivity
-            else:  # (its value, not kept on the object)
-                backward_weights = backward_weights._dense if backward_weights._dense is not None else (0.0 * backward_weights.logits).sigmoid()
+        backward_weights, sens = _peek_weights(backward_weights)
         if backward_weights is not None:
             backward_weights = backward_weights.detach()
         if lazy:
@@ -648,9 +647,7 @@ def focal_sweep(depths: Tensor, weights, backward_flow: Tensor, focal_length_can
         if not torch.is_tensor(depths) or not torch.is_tensor(backward_flow) or not torch.is_tensor(focal_length_candidates):
             raise RuntimeError("flowmap_amd: focal_sweep: depths, backward_flow and focal_length_candidates must be tensors")
         dev = depths.device
-        if dev.type != "cuda" and not using_test_double():
-            raise RuntimeError(f"flowmap_amd: focal_sweep: tensors are on {dev}; it runs on the GPU only (device 'cuda' on ROCm) — the reference has no "
-                               "function that returns this quantity, so host tensors have nowhere to go. There is no CPU fallback.")
+        _refuse_host("focal_sweep", dev)
         if depths.dim() != 4:
             raise RuntimeError(f"flowmap_amd: focal_sweep: depths of shape {tuple(depths.shape)}; expected (batch, frame, height, width)")
         b, f, h, w = depths.shape
@@ -666,27 +663,14 @@ def focal_sweep(depths: Tensor, weights, backward_flow: Tensor, focal_length_can
                             ("weights", weights.logits if isinstance(weights, LazyWeights) else weights)):
             if value.dtype != torch.float32:
                 raise RuntimeError(f"flowmap_amd: focal_sweep: {name} must be float32 (got {value.dtype})")
-        if indices is not None:
-            if not torch.is_tensor(indices) or indices.dtype != torch.int64:
-                raise RuntimeError(f"flowmap_amd: focal_sweep: indices must be an int64 tensor (got {getattr(indices, 'dtype', type(indices).__name__)})")
-            if indices.device != dev:
-                raise RuntimeError(f"flowmap_amd: focal_sweep: indices are on {indices.device}, the depths on {dev}")
-            if indices.dim() != 1 or indices.numel() == 0:
-                raise RuntimeError(f"flowmap_amd: focal_sweep: indices must be a non-empty 1-D tensor (got shape {tuple(indices.shape)})")
-        from ..loss.loss_flow import LossFlow  # (the one parser of ``pairs``; imported here: the loss modules import this one)
-
-        first, count = LossFlow._pair_window(pairs, f - 1)
+        _check_indices("focal_sweep", indices, dev)
+        first, count = parse_window(pairs, f - 1, "focal_sweep", "pairs")
         if b * count > 65535:
             raise ValueError(f"flowmap_amd: focal_sweep: batch x pairs = {b * count} exceeds the 65 535 (batch entry, pair) rows of one call: "
                              "ask for a window of pairs")
         if indices is None:
             indices = _ops.random_subset(h * w, min(h * w if num_points is None else int(num_points), h * w), dev, seed=int(seed))
-        sens = 0.0
-        if isinstance(weights, LazyWeights):
-            if weights.sensitivity != 0.0:
-                weights, sens = weights.logits, weights.sensitivity
-            else:  # (its value, not kept on the object)
-                weights = weights._dense if weights._dense is not None else (0.0 * weights.logits).sigmoid()
+        weights, sens = _peek_weights(weights)
         from .model import focal_lengths_to_intrinsics
 
         candidates = focal_length_candidates.detach()

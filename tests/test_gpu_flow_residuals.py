@@ -10,8 +10,10 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 
-# (batch, frames, h, w, a K per frame)
-SHAPES = [(1, 2, 5, 7, False), (1, 5, 17, 23, True), (1, 6, 24, 32, False), (1, 4, 64, 128, True), (1, 2, 27, 76, False), (1, 2, 7, 292, True), (2, 4, 9, 12, True)]
+# (batch, frames, h, w, a K per frame); the last two reach the second stage of the sums past one batch of 64 slots: 65 workgroups per
+# pair, the last half full (a second trip of one slot), and 64 exactly — only test_sums_repeats_and_windows_gpu takes them
+SHAPES = [(1, 2, 5, 7, False), (1, 5, 17, 23, True), (1, 6, 24, 32, False), (1, 4, 64, 128, True), (1, 2, 27, 76, False), (1, 2, 7, 292, True), (2, 4, 9, 12, True),
+          (1, 4, 258, 512, False), (1, 2, 256, 512, False)]
 
 
 @pytest.mark.parametrize("kind", fr.KINDS)

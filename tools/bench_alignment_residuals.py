@@ -17,33 +17,17 @@ one JSON line (medians and the spread over the rounds); needs a GPU.  No test ga
 from __future__ import annotations
 
 import argparse
-import json
-import statistics
-import subprocess
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
-HBM_PEAK = 8.0e12  # bytes/s (MI355X)
+import _bench_common as bc  # noqa: E402
+from _bench_common import HBM_PEAK, timed  # noqa: E402
+
 READ_BYTES = 4 + 8 + 4 + 4  # later depth, flow, weight, earlier depth (once per pixel)
 FUSED = ("dense", "dense_offsets", "dense_no_sums", "window8_offsets", "indices1000_offsets")
-
-
-def timed(fn, iters, warmup=2):
-    import torch
-
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(end) / iters  # ms
 
 
 def torch_composition(depth, k, rel, bwd, weights, window):
@@ -117,7 +101,7 @@ def child(args):
         ms = timed(lambda: torch_composition(depth, k, rel, bwd, weights, args.torch_window), args.general_iters, warmup=1)
         result["dense_offsets"] = {"ms": ms, "window_frames": args.torch_window, "peak_extra_GB": (torch.cuda.max_memory_allocated() - base) / 1e9}
     result["device"] = torch.cuda.get_device_name(0)
-    print("RESULT " + json.dumps(result), flush=True)
+    bc.print_child_result(result)
 
 
 def main():
@@ -135,35 +119,15 @@ def main():
     args = ap.parse_args()
     if args.child:
         return child(args)
-    runs = {"fused": [], "torch": []}
-    common = [sys.executable, str(Path(__file__).resolve()), "--frames", str(args.frames), "--height", str(args.height), "--width", str(args.width),
-              "--iters", str(args.iters), "--general-iters", str(args.general_iters), "--torch-window", str(args.torch_window)]
-    for _ in range(args.rounds):
-        for route in ("fused", "torch"):
-            # a fresh process per measurement, under its own limit; a failure or a timeout ends the run (nothing more is started on the GPU)
-            done = subprocess.run(common + ["--child", route], capture_output=True, text=True, timeout=args.step_timeout)
-            lines = [x for x in done.stdout.splitlines() if x.startswith("RESULT ")]
-            if done.returncode != 0 or not lines:
-                sys.stderr.write(done.stdout[-2000:] + done.stderr[-2000:])
-                raise SystemExit(f"bench_alignment_residuals: the {route} measurement failed (exit status {done.returncode}); stopping")
-            runs[route].append(json.loads(lines[-1][len("RESULT "):]))
-
-    def summary(route, name):
-        ms = [r[name]["ms"] for r in runs[route]]
-        out = dict(runs[route][0][name], ms=round(statistics.median(ms), 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4))
-        if "share_of_hbm_peak" in out:  # at the median time
-            out["share_of_hbm_peak"] = out["share_of_hbm_peak"] * runs[route][0][name]["ms"] / statistics.median(ms)
-        return {key: (round(v, 4) if isinstance(v, float) else v) for key, v in out.items()}
-
+    common = ["--frames", str(args.frames), "--height", str(args.height), "--width", str(args.width), "--iters", str(args.iters),
+              "--general-iters", str(args.general_iters), "--torch-window", str(args.torch_window)]
+    runs = bc.child_rounds("bench_alignment_residuals", __file__, common, ("fused", "torch"), args.rounds, args.step_timeout)
     first = runs["fused"][0]
     result = {"frames": args.frames, "height": args.height, "width": args.width, "device": first["device"], "rounds": args.rounds,
-              "fused": {name: summary("fused", name) for name in FUSED}, "torch": {"dense_offsets": summary("torch", "dense_offsets")}}
+              "fused": {name: bc.summary(runs["fused"], name, scale_to_median=("share_of_hbm_peak",)) for name in FUSED},
+              "torch": {"dense_offsets": bc.summary(runs["torch"], "dense_offsets")}}
     result["torch_over_fused"] = round(result["torch"]["dense_offsets"]["ms"] / result["fused"]["dense_offsets"]["ms"], 1)
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(line + "\n")
+    bc.emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -12,7 +12,7 @@ existed (they are unchanged by it), timed the same way, with the peak memory tor
 from __future__ import annotations
 
 import argparse
-import json
+import functools
 import sys
 from pathlib import Path
 
@@ -21,20 +21,10 @@ sys.path.insert(0, str(ROOT))
 
 import torch  # noqa: E402
 
-HBM_PEAK = 8.0e12  # bytes/s (MI355X)
+import _bench_common as bc  # noqa: E402
+from _bench_common import HBM_PEAK  # noqa: E402
 
-
-def timed(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(end) / iters  # ms
+timed = functools.partial(bc.timed, warmup=3)
 
 
 def main():
@@ -98,11 +88,7 @@ def main():
                               "ratio_to_residuals": round(ms / result["residuals"]["ms"], 1)}
     fwd, bwd = general()
     result["max_rel_diff_to_general"] = max(float((a - b).norm() / b.norm()) for a, b in ((fused.forward, fwd), (fused.backward, bwd)))
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(line + "\n")
+    bc.emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -19,14 +19,14 @@ from __future__ import annotations
 
 import argparse
 import csv
-import json
-import statistics
-import subprocess
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+
+import _bench_common as bc  # noqa: E402
+from _bench_common import timed  # noqa: E402
 
 GATHER_BYTES = (8 + 4 + 4 + 8 + 16) + (8 + 4 + 4 + 8)  # per (pair, candidate, correspondence), both passes
 NAMES = ("all_pairs", "all_pairs_points", "one_pair")
@@ -44,21 +44,6 @@ def profiled_forward_us():
             if len(row) >= 4 and any(row[0].startswith(name) for name in SWEEP_FORWARD_KERNELS):
                 total += float(row[3])
     return round(total, 2)
-
-
-def timed(fn, iters, warmup=2):
-    import torch
-
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(end) / iters  # ms
 
 
 def child(args):
@@ -100,7 +85,7 @@ def child(args):
             result["all_pairs"] = {"ms": timed(lambda: [pair(i) for i in range(f - 1)], max(1, args.iters // 4))}
             result["one_pair"] = {"ms": timed(lambda: pair(middle), args.iters)}
     result["device"] = torch.cuda.get_device_name(0)
-    print("RESULT " + json.dumps(result), flush=True)
+    bc.print_child_result(result)
 
 
 def main():
@@ -118,38 +103,19 @@ def main():
     args = ap.parse_args()
     if args.child:
         return child(args)
-    runs = {"fused": [], "composed": []}
-    common = [sys.executable, str(Path(__file__).resolve())]
+    common = []
     for key in ("frames", "height", "width", "points", "candidates", "iters"):
         common += [f"--{key}", str(getattr(args, key))]
-    for _ in range(args.rounds):
-        for route in ("fused", "composed"):
-            # a fresh process per measurement, under its own limit; a failure or a timeout ends the run (nothing more is started on the GPU)
-            done = subprocess.run(common + ["--child", route], capture_output=True, text=True, timeout=args.step_timeout)
-            lines = [x for x in done.stdout.splitlines() if x.startswith("RESULT ")]
-            if done.returncode != 0 or not lines:
-                sys.stderr.write(done.stdout[-2000:] + done.stderr[-2000:])
-                raise SystemExit(f"bench_focal_sweep: the {route} measurement failed (exit status {done.returncode}); stopping")
-            runs[route].append(json.loads(lines[-1][len("RESULT "):]))
-
-    def summary(route, name):
-        ms = [r[name]["ms"] for r in runs[route]]
-        out = {"ms": round(statistics.median(ms), 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4)}
-        if "gathered_GBps" in runs[route][0][name]:
-            out["gathered_GBps"] = round(statistics.median(r[name]["gathered_GBps"] for r in runs[route]), 1)
-        return out
-
+    runs = bc.child_rounds("bench_focal_sweep", __file__, common, ("fused", "composed"), args.rounds, args.step_timeout)
     first = runs["fused"][0]
     result = {"frames": args.frames, "height": args.height, "width": args.width, "points": first["points"], "candidates": first["candidates"],
-              "device": first["device"], "rounds": args.rounds, "fused": {name: summary("fused", name) for name in NAMES},
-              "composed": {name: summary("composed", name) for name in ("all_pairs", "one_pair")}, "profiled_sweep_forward_kernels_us": profiled_forward_us()}
+              "device": first["device"], "rounds": args.rounds,
+              "fused": {name: bc.summary(runs["fused"], name, scale_to_median=("gathered_GBps",)) for name in NAMES},
+              "composed": {name: bc.summary(runs["composed"], name) for name in ("all_pairs", "one_pair")},
+              "profiled_sweep_forward_kernels_us": profiled_forward_us()}
     for name in ("all_pairs", "one_pair"):
         result[f"composed_over_fused_{name}"] = round(result["composed"][name]["ms"] / result["fused"][name]["ms"], 2)
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(line + "\n")
+    bc.emit(result, args.out)
 
 
 if __name__ == "__main__":

@@ -16,31 +16,14 @@ rounds); needs a GPU.  No test gates on its numbers.
 from __future__ import annotations
 
 import argparse
-import json
-import statistics
-import subprocess
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
-HBM_PEAK = 8.0e12  # bytes/s (MI355X)
-
-
-def timed(fn, iters, warmup=2):
-    import torch
-
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(end) / iters  # ms
+import _bench_common as bc  # noqa: E402
+from _bench_common import HBM_PEAK, timed  # noqa: E402,F401
 
 
 def make_tracks(f, dev, seed=0, interval=5, radius=20, grid=35):
@@ -103,7 +86,7 @@ def child(args):
         result["all"] = {"ms": timed(lambda: loss.residuals(batch, tracks, out), args.general_iters, warmup=1),
                          "peak_extra_GB": (torch.cuda.max_memory_allocated() - base) / 1e9, "surfaces_GB": surfaces.numel() * 4 / 1e9}
     result["device"] = torch.cuda.get_device_name(0)
-    print("RESULT " + json.dumps(result), flush=True)
+    bc.print_child_result(result)
 
 
 def main():
@@ -120,35 +103,16 @@ def main():
     args = ap.parse_args()
     if args.child:
         return child(args)
-    runs = {"fused": [], "general": []}
-    common = [sys.executable, str(Path(__file__).resolve()), "--frames", str(args.frames), "--height", str(args.height), "--width", str(args.width),
-              "--iters", str(args.iters), "--general-iters", str(args.general_iters)]
-    for _ in range(args.rounds):
-        for route in ("fused", "general"):
-            # a fresh process per measurement, under its own limit; a failure or a timeout ends the run (nothing more is started on the GPU)
-            done = subprocess.run(common + ["--child", route], capture_output=True, text=True, timeout=args.step_timeout)
-            lines = [x for x in done.stdout.splitlines() if x.startswith("RESULT ")]
-            if done.returncode != 0 or not lines:
-                sys.stderr.write(done.stdout[-2000:] + done.stderr[-2000:])
-                raise SystemExit(f"bench_track_residuals: the {route} measurement failed (exit status {done.returncode}); stopping")
-            runs[route].append(json.loads(lines[-1][len("RESULT "):]))
-
-    def summary(route, name):
-        ms = [r[name]["ms"] for r in runs[route]]
-        out = dict(runs[route][0][name], ms=round(statistics.median(ms), 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4))
-        return {key: (round(v, 4) if isinstance(v, float) else v) for key, v in out.items()}
-
+    common = ["--frames", str(args.frames), "--height", str(args.height), "--width", str(args.width), "--iters", str(args.iters),
+              "--general-iters", str(args.general_iters)]
+    runs = bc.child_rounds("bench_track_residuals", __file__, common, ("fused", "general"), args.rounds, args.step_timeout)
     first = runs["fused"][0]
     result = {"frames": args.frames, "height": args.height, "width": args.width, "device": first["device"], "rounds": args.rounds,
               "segments": first["segments"], "elements_all": first["elements_all"], "elements_one": first["elements_one"],
-              "fused": {name: summary("fused", name) for name in ("one", "one_predicted", "all", "all_predicted", "all_no_sums")},
-              "general": {name: summary("general", name) for name in ("one", "all")}}
+              "fused": {name: bc.summary(runs["fused"], name) for name in ("one", "one_predicted", "all", "all_predicted", "all_no_sums")},
+              "general": {name: bc.summary(runs["general"], name) for name in ("one", "all")}}
     result["general_over_fused"] = {name: round(result["general"][name]["ms"] / result["fused"][name]["ms"], 1) for name in ("one", "all")}
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(line + "\n")
+    bc.emit(result, args.out)
 
 
 if __name__ == "__main__":
