@@ -66,7 +66,7 @@ def parse_window(selection, total: int, what: str, noun: str, allow_int: bool = 
     else:
         raise ValueError(f"flowmap_amd: {what}: {noun} must be {forms}, got {selection!r}")
     if first < 0 or count < 1 or first + count > total:
-        where = "the video" if noun == "pairs" else "the track list"
+        where = "the video" if noun in ("pairs", "frames") else "the track list"
         raise ValueError(f"flowmap_amd: {what}: the {noun} [{first}, {first + count}) do not lie in the {total} {noun} of {where}")
     return int(first), int(count)
 

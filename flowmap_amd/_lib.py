@@ -123,6 +123,8 @@ SIGNATURES = {
     "fm_alignment_residual_workspace": [L, P],
     "fm_alignment_residuals": [P] * 5 + [F, P, P, L, I, I, I, I, I, I] + [P] * 7,
     "fm_focal_sweep": [P, P, F, P, P, L, P, P, P, I, I, I, I, I, I, I] + [P] * 7,
+    "fm_depth_consistency_blocks": [I, I, P],
+    "fm_depth_consistency": [P] * 5 + [I] * 7 + [F] + [P] * 11,
 }
 
 _lib: Optional[ctypes.CDLL] = None

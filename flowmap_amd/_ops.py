@@ -241,7 +241,8 @@ def _dense_flow_is_rough(bwd_flow: Tensor, h: int, w: int) -> bool:
 
 # which backward path the facades selected (tests)
 counters = {"procrustes_planned": 0, "procrustes_dense_planned": 0, "flow_packs": 0, "flow_packs_bitmask": 0, "procrustes_plans_built": 0, "track_tap_samples": 0,
-            "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0, "flow_residuals": 0, "track_residuals": 0, "alignment_residuals": 0, "focal_sweep": 0}
+            "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0, "flow_residuals": 0, "track_residuals": 0, "alignment_residuals": 0, "focal_sweep": 0,
+            "depth_consistency": 0}
 
 
 class LeadingFrames:
@@ -863,6 +864,18 @@ def focal_sweep(depth, weights, weight_sens, bwd_flow, indices, focal_lengths, c
              ptr(point_error), stream_for(depth))
     counters["focal_sweep"] += 1
     return error, soft, focal, intrinsics, pose_out, point_error
+
+
+def depth_consistency(depth, k, kinv, ext, offsets, first_frame, count, tolerance, details, sums):
+    """The depth consistency of the source frames [first_frame, first_frame + count) at the frame offsets ``offsets`` (csrc/fm_torch.cpp:
+    depth_consistency_op -> fm_depth_consistency): (error, code, positions, reprojected, sampled, support, frame_sum, frame_valid), None
+    for what was not asked for (``tolerance`` None: no support).  One small launch for the window's relative poses, one pass over depth,
+    the ordered second stage of the sums.  Reads its arguments and nothing else: no DepthSink, no tap plan, no optimiser ticket, no note
+    on any tensor."""
+    out = torch_ops().depth_consistency(depth, k, kinv, ext, [int(d) for d in offsets], int(first_frame), int(count),
+                                        -1.0 if tolerance is None else float(tolerance), bool(details), bool(sums))
+    counters["depth_consistency"] += 1
+    return tuple(x if x.numel() else None for x in out)
 
 
 def softmin_intrinsics(depth, weights, bwd_flow, indices, candidate_k, rel, weight_sens, frames):

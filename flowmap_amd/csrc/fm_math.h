@@ -506,6 +506,46 @@ FM_HD FlowResidual flow_residual_at(const DirConst& d, float arow, float brow, f
 }
 
 // ---------------------------------------------------------------------------------
+// Depth consistency of ONE source pixel against ONE target frame j (projection.depth_consistency; fm_depth_consistency.hip and its
+// host twin both call this):
+//   p = z·K_i⁻¹[u,v,1] (unproject, projection.py:76-90; `ray` is K_i⁻¹[u,v,1]),  q = (E_j⁻¹E_i)·[p;1] (projection.py:154,288),
+//   uv = project_camera_space(q, K_j) (projection.py:49-58: ε = 1e-5, ±1e8 / NaN -> 0),
+//   ẑ = grid_sample(depth_j, uv·2−1, bilinear, border, align_corners=False) (projection.py:235-241,266-272),
+//   code = 2 when not q.z > 0, else 3 when not 0 <= uv < 1 in both coordinates (projection.py:294-295), else 0,
+//   error = (ẑ − q.z)/q.z where code == 0, else exactly 0.
+// A missing target (code 1) is the caller's: it does not call this.  `depth_j` addresses frame j's (h, w) depth; whatever uv holds,
+// the taps are clamped into the frame and a tap outside it is not read.
+// ---------------------------------------------------------------------------------
+struct DepthConsistencyTerm {
+  float error, u, v, qz, sampled;
+  int code;
+};
+
+FM_HD DepthConsistencyTerm depth_consistency_at(const float ray[3], float z, const Pose& rel, const Mat3& kj, const float* depth_j, int h, int w) {
+  float p[3], q[3];
+  p[0] = ray[0] * z;
+  p[1] = ray[1] * z;
+  p[2] = ray[2] * z;
+  apply_pose(rel, p, q);
+  const Projected pr = project_point(q, kj);
+  const Taps taps = bilinear_taps(pr.u, pr.v, h, w);
+  float zs = 0.f;
+  for (int t = 0; t < 4; ++t) {
+    if (!taps.in[t]) continue;
+    zs += depth_j[(size_t)tap_row(taps, t) * w + tap_col(taps, t)] * taps.w[t];
+  }
+  DepthConsistencyTerm o;
+  o.u = pr.u;
+  o.v = pr.v;
+  o.qz = q[2];
+  o.sampled = zs;
+  const bool inside = pr.u >= 0.f && pr.u < 1.f && pr.v >= 0.f && pr.v < 1.f;
+  o.code = !(q[2] > 0.f) ? 2 : (inside ? 0 : 3);
+  o.error = o.code == 0 ? (zs - q[2]) / q[2] : 0.f;
+  return o;
+}
+
+// ---------------------------------------------------------------------------------
 // One (candidate, sampled pixel) term of IntrinsicsSoftmin's score (intrinsics_softmin.py:105-121):
 //   X = z·K⁻¹[u,v,1] (unproject the later frame's pixel), X' = T·X (fitted pose, later -> earlier),
 //   xy = project_camera_space(X', K) (exact ±1e8 / NaN->0 semantics), flow = xy − (u,v),
@@ -1056,6 +1096,21 @@ FM_HD void mat4_mul_nt(const double* a, const double* b, double* o) {  // a bᵀ
     }
 }
 
+// One row of the pose table of the depth consistency (fm_depth_consistency): the relative pose E_j⁻¹·E_i of two camera-to-world
+// matrices (row-major 4x4; projection.py:154,288), formed in fp64 and rounded once.  out[15] is the row's flag: 1 here, 0 where the
+// target frame does not exist (a pose's last row is 0 0 0 1 and is never read).
+FM_HD void depth_consistency_pose(const float* e_i, const float* e_j, float* out) {
+  double a[16], b[16], inv[16], m[16];
+  for (int i = 0; i < 16; ++i) {
+    a[i] = e_i[i];
+    b[i] = e_j[i];
+  }
+  inv4(b, inv);
+  mat4_mul(inv, a, m);
+  for (int i = 0; i < 15; ++i) out[i] = (float)m[i];
+  out[15] = 1.f;
+}
+
 
 // ---------------------------------------------------------------------------------
 // Dense Procrustes (`num_points: null`: every pixel of every pair is a correspondence,
@@ -1306,4 +1361,5 @@ FM_HD void dense_bwd_s(const DenseBwd& c, const float h[3], const float t[3], co
 #include "fm_flow_residuals_host.h"
 #include "fm_alignment_residuals_host.h"
 #include "fm_focal_sweep_host.h"
+#include "fm_depth_consistency_host.h"
 #endif

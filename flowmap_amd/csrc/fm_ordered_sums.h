@@ -1,4 +1,5 @@
-// The ordered two-stage fp64 sum of the residual passes (fm_flow_residuals.hip, fm_alignment_residuals.hip): no atomics.
+// The ordered two-stage fp64 sum of the residual passes (fm_flow_residuals.hip, fm_alignment_residuals.hip, fm_depth_consistency.hip):
+// no atomics.
 //
 // Stage 1, at the end of the map kernel: a thread has added its terms in fp64; the wave butterfly and the workgroup's wave totals follow
 // in fp64, and thread 0 leaves the workgroup's pair of doubles in the workgroup's OWN workspace slot with one 16-byte store.  Stage 2,
@@ -30,6 +31,38 @@ __device__ __forceinline__ void block_sum_to_slot(double a, double b, double* sl
       tot.y += red[w][1];
     }
     *reinterpret_cast<double2*>(slot) = tot;  // a plain 16-byte store, no atomics
+  }
+}
+
+// Stage 1 for a workgroup that owns the same elements in up to ROWS rows (fm_depth_consistency.hip: one row per frame offset).  In round
+// `row` every thread calls wave_partial_to_lds — wave butterflies only, no barrier between the rounds —, then, once, every thread calls
+// block_rows_to_slots (one __syncthreads): thread r adds row r's wave partials in ascending wave order, exactly the additions of
+// block_sum_to_slot, and leaves them in the slot of row r, `slot_stride` doubles after row r − 1's.
+template <int THREADS, int ROWS>
+struct RowPartials {
+  double v[ROWS][THREADS / kWave][2];
+};
+
+template <int THREADS, int ROWS>
+__device__ __forceinline__ void wave_partial_to_lds(RowPartials<THREADS, ROWS>& lds, int row, double a, double b) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    lds.v[row][threadIdx.x >> 6][0] = a;
+    lds.v[row][threadIdx.x >> 6][1] = b;
+  }
+}
+
+template <int THREADS, int ROWS>
+__device__ __forceinline__ void block_rows_to_slots(const RowPartials<THREADS, ROWS>& lds, int rows, double* slot0, size_t slot_stride) {
+  __syncthreads();
+  if ((int)threadIdx.x < rows) {
+    double2 tot = make_double2(0.0, 0.0);
+    for (int w = 0; w < THREADS / kWave; ++w) {
+      tot.x += lds.v[threadIdx.x][w][0];
+      tot.y += lds.v[threadIdx.x][w][1];
+    }
+    *reinterpret_cast<double2*>(slot0 + threadIdx.x * slot_stride) = tot;  // a plain 16-byte store, no atomics
   }
 }
 

@@ -1,5 +1,5 @@
 // Argument checks and size formulas of the residual entry points (include/flowmap_hip.h: fm_flow_residuals, fm_track_residuals,
-// fm_alignment_residuals, fm_focal_sweep and their size functions), stated ONCE: the device build (fm_*.hip) and the serial host build of
+// fm_alignment_residuals, fm_focal_sweep, fm_depth_consistency and their size functions), stated ONCE: the device build (fm_*.hip) and the serial host build of
 // the same ABI (fm_*_host.h) both call these, so the two refuse the same calls and size the same workspaces.  Plain C++, no HIP.
 // Device-only, and therefore not here: the 16-byte path's eligibility and the pointer alignment the kernels need (the host build reads
 // element by element and never touches the workspace).
@@ -104,6 +104,33 @@ static inline bool focal_sweep_args_ok(const float* depth, const float* weights,
   if (!(error && soft && focal && intrinsics)) return false;
   if (!res_frame_ok(height, width) || !res_window_ok(batch, frames, first_pair, count)) return false;
   return res_points_ok(points) && candidates >= 1;
+}
+
+// ---- depth consistency ----
+constexpr int kDepthConsTile = 1024;       // pixels per workgroup of depth_consistency_kernel
+constexpr int kDepthConsMaxOffsets = 8;    // frame offsets of one call
+static inline long depth_consistency_blocks(long pixels) { return (pixels + kDepthConsTile - 1) / kDepthConsTile; }
+static inline bool depth_consistency_blocks_args_ok(int height, int width, const int* blocks) { return blocks && res_frame_ok(height, width); }
+
+static inline bool depth_consistency_args_ok(const float* depth, const float* k, const float* kinv, const float* ext, const int32_t* offsets, int n_offsets,
+                                             int batch, int frames, int height, int width, int first_frame, int count, float tolerance, const float* error,
+                                             const uint8_t* code, const float* positions, const float* reprojected, const float* sampled,
+                                             const uint8_t* support, const double* frame_sum, const double* frame_valid, const float* rel,
+                                             const double* workspace) {
+  if (!(depth && k && kinv && ext && offsets && error && code && rel)) return false;
+  if ((positions != nullptr) != (reprojected != nullptr) || (positions != nullptr) != (sampled != nullptr)) return false;
+  const bool sums = frame_sum != nullptr;
+  if ((frame_valid != nullptr) != sums || (workspace != nullptr) != sums) return false;
+  if (support && !(tolerance >= 0.f)) return false;
+  if (!res_frame_ok(height, width)) return false;
+  if (!(batch >= 1 && frames >= 2 && first_frame >= 0 && count >= 1 && (long)first_frame + count <= frames && (long)batch * count <= kResMaxRows)) return false;
+  if (n_offsets < 1 || n_offsets > kDepthConsMaxOffsets) return false;
+  for (int i = 0; i < n_offsets; ++i) {
+    if (offsets[i] == 0 || offsets[i] <= -frames || offsets[i] >= frames) return false;
+    for (int j = 0; j < i; ++j)
+      if (offsets[j] == offsets[i]) return false;
+  }
+  return true;
 }
 
 }  // namespace fm

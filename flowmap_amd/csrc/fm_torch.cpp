@@ -50,7 +50,8 @@ using OptTensor = std::optional<Tensor>;
   X(fm_depth_gather) X(fm_extrinsics_inverse) X(fm_track_loss_fused_fwd) X(fm_track_loss_bwd) X(fm_adam_step)                 \
   X(fm_adam_step_capturable) X(fm_softmin_score_fwd) X(fm_softmin_score_bwd) X(fm_softmin_blend_fwd) X(fm_softmin_blend_bwd)         \
   X(fm_random_subset) X(fm_random_subset_stateful) X(fm_abi_version) X(fm_flow_loss_fused_taps) X(fm_track_loss_fused_fwd_taps) X(fm_tap_grad_apply) \
-  X(fm_flow_loss_fused_bitmask) X(fm_flow_residuals) X(fm_flow_residual_blocks) X(fm_track_residuals) X(fm_track_residual_workspace)
+  X(fm_flow_loss_fused_bitmask) X(fm_flow_residuals) X(fm_flow_residual_blocks) X(fm_track_residuals) X(fm_track_residual_workspace) \
+  X(fm_depth_consistency) X(fm_depth_consistency_blocks)
 
 struct Api {
 #define X(name) decltype(&::name) name = nullptr;
@@ -1628,6 +1629,58 @@ static std::vector<Tensor> track_residuals_op(const Tensor& depth_in, const Tens
   return {residual, visible, xy_target, pair_sum, pair_count, track_sum, track_count};
 }
 
+// projection.depth_consistency (fm_depth_consistency): per source pixel of a window of frames and per frame offset the relative error of the
+// target frame's depth, sampled where the pixel reprojects under the chained poses, against the depth the reprojection predicts, with its
+// code; optionally uv / q.z / the sample, the per-pixel support under a tolerance (tolerance < 0: none) and the per-row fp64 sums.  Not
+// differentiable.  -> {error, code, positions, reprojected, sampled, support, frame_sum, frame_valid}; what was not asked for comes back
+// as an empty tensor.  The pose rows and the sums' workspace are this call's only scratch.
+static std::vector<Tensor> depth_consistency_op(const Tensor& depth_in, const Tensor& k_in, const Tensor& kinv_in, const Tensor& ext_in, std::vector<int64_t> offsets,
+                                                int64_t first_frame, int64_t count, double tolerance, bool details, bool sums) {
+  at::NoGradGuard no_grad;
+  const auto dev = check_device({&depth_in, &k_in, &kinv_in, &ext_in});
+  const Tensor depth = f32c(depth_in.detach(), "depth"), k = f32c(k_in.detach(), "intrinsics"), kinv = f32c(kinv_in.detach(), "inverse intrinsics"),
+               ext = f32c(ext_in.detach(), "extrinsics");
+  TORCH_CHECK(depth.dim() == 4, "flowmap_amd: depth must be (batch, frame, height, width)");
+  const int64_t b = depth.size(0), f = depth.size(1), h = depth.size(2), w = depth.size(3), n_off = (int64_t)offsets.size();
+  TORCH_CHECK(h * w < (int64_t(1) << 30), "flowmap_amd: the depth consistency indexes pixels inside a frame with 32 bits: height x width = ", h * w,
+              " must stay below 2^30");
+  TORCH_CHECK(k.sizes() == at::IntArrayRef({b, f, 3, 3}) && kinv.sizes() == k.sizes() && ext.sizes() == at::IntArrayRef({b, f, 4, 4}),
+              "flowmap_amd: intrinsics / extrinsics shapes do not match depth");
+  TORCH_CHECK(n_off >= 1 && n_off <= 8, "flowmap_amd: the depth consistency takes 1 to 8 offsets (got ", n_off, ")");
+  TORCH_CHECK(f >= 2 && first_frame >= 0 && count >= 1 && first_frame + count <= f, "flowmap_amd: the frame window [", first_frame, ", ", first_frame + count,
+              ") does not lie in the ", f, " frames");
+  TORCH_CHECK(b * count <= 65535, "flowmap_amd: the depth consistency handles at most 65 535 frames per call (batch x frames = ", b * count, "): split the window");
+  int32_t off[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int64_t i = 0; i < n_off; ++i) {
+    TORCH_CHECK(offsets[i] != 0 && offsets[i] > -f && offsets[i] < f, "flowmap_amd: the depth consistency takes non-zero offsets with |d| <= frames - 1 (got ", offsets[i], ")");
+    off[i] = (int32_t)offsets[i];
+  }
+  const auto fopt = depth.options(), bopt = fopt.dtype(at::kByte), dopt = fopt.dtype(at::kDouble);
+  const bool tol = tolerance >= 0.0;
+  Tensor error = at::empty({b, count, n_off, h, w}, fopt), code = at::empty({b, count, n_off, h, w}, bopt);
+  Tensor positions = at::empty({0}, fopt), reprojected = positions, sampled = positions, support = at::empty({0}, bopt);
+  Tensor frame_sum = at::empty({0}, dopt), frame_valid = frame_sum, work, rel = at::empty({b, count, n_off, 16}, fopt);
+  if (details) {
+    positions = at::empty({b, count, n_off, h, w, 2}, fopt);
+    reprojected = at::empty({b, count, n_off, h, w}, fopt);
+    sampled = at::empty({b, count, n_off, h, w}, fopt);
+  }
+  if (tol) support = at::empty({b, count, h, w}, bopt);
+  if (sums) {
+    int blocks = 0;
+    FM_CALL(fm_depth_consistency_blocks, (int)h, (int)w, &blocks);
+    frame_sum = at::empty({b, count, n_off}, dopt);
+    frame_valid = at::empty({b, count, n_off}, dopt);
+    work = at::empty({b * count * n_off * (int64_t)blocks * 2}, dopt);
+  }
+  DeviceScope scope(dev);
+  FM_CALL(fm_depth_consistency, ptr(depth), ptr(k), ptr(kinv), ptr(ext), off, (int)n_off, (int)b, (int)f, (int)h, (int)w, (int)first_frame, (int)count,
+          tol ? (float)tolerance : 0.f, ptr(error), ptr<uint8_t>(code), details ? ptr(positions) : nullptr, details ? ptr(reprojected) : nullptr,
+          details ? ptr(sampled) : nullptr, tol ? ptr<uint8_t>(support) : nullptr, sums ? ptr<double>(frame_sum) : nullptr,
+          sums ? ptr<double>(frame_valid) : nullptr, ptr(rel), sums ? ptr<double>(work) : nullptr, scope.stream);
+  return {error, code, positions, reprojected, sampled, support, frame_sum, frame_valid};
+}
+
 }  // namespace fmt
 
 TORCH_LIBRARY(flowmap_amd, m) {
@@ -1709,4 +1762,7 @@ TORCH_LIBRARY(flowmap_amd, m) {
   m.def("track_residuals(Tensor depth, Tensor k, Tensor kinv, Tensor ext, Tensor xy, Tensor vis, Tensor seg, int[] counts, int[] seg_frames, int[] seg_points, "
         "int first, int kind, float delta, bool predicted, bool sums) -> Tensor[]",
         fmt::track_residuals_op);
+  m.def("depth_consistency(Tensor depth, Tensor k, Tensor kinv, Tensor ext, int[] offsets, int first_frame, int count, float tolerance, bool details, "
+        "bool sums) -> Tensor[]",
+        fmt::depth_consistency_op);
 }

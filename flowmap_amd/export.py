@@ -24,10 +24,13 @@ from . import _ops
 from ._lib import call, check_device, ptr, stream_for
 
 
-def world_point_cloud(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, colors: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
+def world_point_cloud(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, colors: Optional[Tensor] = None,
+                      keep: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
     """depths (F,H,W), intrinsics (F,3,3), extrinsics (F,4,4) camera-to-world, colors
     (F,3,H,W) -> world points (F·H·W,3) and colours (F·H·W,3), frames concatenated in order
-    (colmap.py:86-101 with ``exports.*[0]``)."""
+    (colmap.py:86-101 with ``exports.*[0]``).  ``keep``: a bool (F,H,W) mask on the depths' device — the points and colours
+    returned are the kept ones, in the same order (e.g. ``depth_consistency(...).support[0] >= 2``: the points that at least two
+    other frames confirm); None: every point."""
     check_device(depths, intrinsics, extrinsics, *(() if colors is None else (colors,)))
     if depths.dim() != 3:
         raise RuntimeError("flowmap_amd: depths must be (frame, height, width)")
@@ -36,6 +39,13 @@ def world_point_cloud(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, co
         raise RuntimeError("flowmap_amd: intrinsics / extrinsics do not match the depths")
     if colors is not None and tuple(colors.shape) != (f, 3, h, w):
         raise RuntimeError("flowmap_amd: colors must be (frame, 3, height, width)")
+    if keep is not None:
+        if not torch.is_tensor(keep) or keep.dtype != torch.bool:
+            raise RuntimeError(f"flowmap_amd: keep must be a bool tensor (got {getattr(keep, 'dtype', type(keep).__name__)})")
+        if tuple(keep.shape) != (f, h, w):
+            raise RuntimeError(f"flowmap_amd: keep of shape {tuple(keep.shape)} does not match the depths {(f, h, w)}")
+        if keep.device != depths.device:
+            raise RuntimeError(f"flowmap_amd: keep is on {keep.device}, the depths on {depths.device}")
     with torch.no_grad():
         depths, extrinsics = _ops._f32c(depths, "depths"), _ops._f32c(extrinsics, "extrinsics")
         kinv = _ops.intrinsics_inverse(_ops._f32c(intrinsics, "intrinsics"))
@@ -44,6 +54,9 @@ def world_point_cloud(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, co
         rgb = None if colors is None else torch.empty_like(xyz)
         with _ops._guard(depths.device):
             call("fm_world_points", ptr(depths), ptr(kinv), ptr(extrinsics), ptr(colors), f, h, w, ptr(xyz), ptr(rgb), stream_for(depths))
+        if keep is not None:
+            kept = keep.reshape(-1)
+            xyz, rgb = xyz[kept], None if rgb is None else rgb[kept]
     return xyz, rgb
 
 

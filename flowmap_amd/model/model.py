@@ -20,7 +20,7 @@ from ..types import ModelOutput
 from .backbone import BackboneExplicitDepth, BackboneExplicitDepthCfg  # noqa: F401  (flowmap/model/backbone/backbone_explicit_depth.py)
 from .extrinsics_procrustes import ExtrinsicsProcrustes, ExtrinsicsProcrustesCfg
 from .extrinsics_regressed import ExtrinsicsRegressed, ExtrinsicsRegressedCfg
-from .projection import sample_image_grid, unproject
+from .projection import depth_consistency, sample_image_grid, unproject
 
 
 _K_CONSTANTS: dict = {}
@@ -123,3 +123,8 @@ class Model(nn.Module):
         extrinsics = self.extrinsics.forward(batch, flows, backbone_out, surfaces)
 
         return ModelOutput(backbone_out.depths, surfaces, intrinsics, extrinsics, backbone_out.weights)
+
+    def consistency(self, model_output, **kw):
+        """projection.depth_consistency of a ModelOutput's depths under its intrinsics and extrinsics (``offsets``, ``frames``,
+        ``tolerance``, ``details``, ``sums`` as there) -> DepthConsistency.  It only reads: a LazyExtrinsics stays unevaluated."""
+        return depth_consistency(model_output.depths, model_output.intrinsics, model_output.extrinsics, **kw)

@@ -24,7 +24,7 @@ from torch import Tensor
 from .. import _ops
 from .._base import parse_window
 from .._lib import check_device, using_test_double
-from ..types import AlignmentResiduals, FocalSweep
+from ..types import AlignmentResiduals, DepthConsistency, FocalSweep
 
 # --------------------------------------------------------------------------------------
 # small tensor helpers (no kernels needed: pure indexing / concatenation)
@@ -540,7 +540,7 @@ def align_surfaces(surfaces, backward_flows: Tensor, backward_weights: Tensor, i
     return _align_surfaces(surfaces, backward_flows, backward_weights, indices, lazy_ok=False)
 
 
-# The front door of the two diagnostics below (alignment_residuals, focal_sweep): what they refuse and unwrap alike.
+# The front door of the diagnostics below (alignment_residuals, depth_consistency, focal_sweep): what they refuse and unwrap alike.
 
 
 def _refuse_host(what: str, dev) -> None:
@@ -628,6 +628,122 @@ def alignment_residuals(surfaces, backward_flows: Tensor, backward_weights, extr
         else:
             out = _ops.alignment_residuals(None, None, src.detach(), backward_flows, backward_weights, sens, rel, indices, first, count, offsets, weights, sums)
         return AlignmentResiduals(*out, first)
+
+
+def _check_offsets(offsets, frames: int) -> tuple:
+    is_int = lambda x: isinstance(x, int) and not isinstance(x, bool)  # noqa: E731
+    if not isinstance(offsets, (tuple, list)) or not all(is_int(d) for d in offsets):
+        raise ValueError(f"flowmap_amd: depth_consistency: offsets must be a tuple or list of ints, got {offsets!r}")
+    offsets = tuple(int(d) for d in offsets)
+    if not 1 <= len(offsets) <= 8:
+        raise ValueError(f"flowmap_amd: depth_consistency: between 1 and 8 offsets per call (got {len(offsets)})")
+    if 0 in offsets or len(set(offsets)) != len(offsets):
+        raise ValueError(f"flowmap_amd: depth_consistency: offsets must be distinct and non-zero, got {offsets}")
+    if any(abs(d) > frames - 1 for d in offsets):
+        raise ValueError(f"flowmap_amd: depth_consistency: offsets {offsets} reach past the {frames} frames of the video (|d| <= {frames - 1})")
+    return offsets
+
+
+def _consistency_on_host(ref, depths, intrinsics, extrinsics, offsets, first, count, tolerance, details, sums) -> DepthConsistency:
+    """Host tensors after install(): the same composition from the reference's own functions (``ref``: name -> original)."""
+    b, f, h, w = depths.shape
+    xy, _ = ref("sample_image_grid")((h, w), depths.device)
+    maps = (b, count, len(offsets), h, w)
+    error, code = torch.zeros(maps, dtype=torch.float32), torch.ones(maps, dtype=torch.uint8)
+    uv_out, qz_out, zs_out = (torch.zeros((*maps, 2)), torch.zeros(maps), torch.zeros(maps)) if details else (None, None, None)
+    for o, d in enumerate(offsets):
+        rows = [lf for lf in range(count) if 0 <= first + lf + d < f]
+        if not rows:
+            continue
+        src = [first + lf for lf in rows]
+        dst = [i + d for i in src]
+        points = ref("unproject")(xy, depths[:, src], intrinsics[:, src][:, :, None, None])
+        rel = extrinsics[:, dst].inverse() @ extrinsics[:, src]
+        q = ref("transform_rigid")(ref("homogenize_points")(points), rel[:, :, None, None])[..., :3]
+        uv = ref("project_camera_space")(q, intrinsics[:, dst][:, :, None, None])
+        n = len(rows)
+        zs = torch.nn.functional.grid_sample(depths[:, dst].reshape(b * n, 1, h, w), (uv * 2 - 1).reshape(b * n, h, w, 2), mode="bilinear",
+                                             padding_mode="border", align_corners=False).reshape(b, n, h, w)
+        qz = q[..., 2]
+        inside = (uv >= 0).all(dim=-1) & (uv < 1).all(dim=-1)
+        c = torch.where(~(qz > 0), 2, torch.where(inside, 0, 3)).to(torch.uint8)
+        code[:, rows, o] = c
+        error[:, rows, o] = torch.where(c == 0, (zs - qz) / qz, torch.zeros_like(qz))
+        if details:
+            uv_out[:, rows, o], qz_out[:, rows, o], zs_out[:, rows, o] = uv, qz, zs
+    ok = code == 0
+    support = None if tolerance is None else (ok & (error.abs() <= tolerance)).sum(dim=2).to(torch.uint8)
+    frame_sum = torch.where(ok, error.abs(), torch.zeros_like(error)).to(torch.float64).sum(dim=(3, 4)) if sums else None
+    frame_valid = ok.to(torch.float64).sum(dim=(3, 4)) if sums else None
+    return DepthConsistency(error, code, uv_out, qz_out, zs_out, support, frame_sum, frame_valid, first, offsets)
+
+
+def depth_consistency(depths: Tensor, intrinsics: Tensor, extrinsics, offsets=(-1, 1), frames=None, tolerance: Optional[float] = None,
+                      details: bool = False, sums: bool = True) -> DepthConsistency:
+    """Do the depth maps agree with each other under the chained camera poses, a few frames apart?  For a source frame i of ``frames``, an
+    offset d of ``offsets``, the target frame j = i + d and the pixel with centre xy (``sample_image_grid``):
+
+      p = unproject(xy, depth_i, K_i) (flowmap/model/projection.py:76-90);  q = (E_j⁻¹·E_i)·[p; 1], xyz — the relative transformation
+      ``compute_forward_flow`` / ``compute_track_flow`` form (projection.py:154, :288), at distance d instead of 1;
+      uv = project_camera_space(q, K_j) (projection.py:49-58, its ε = 1e-5 and ±1e8 / NaN clamp);
+      ẑ = grid_sample(depth_j, uv·2−1, bilinear, padding_mode="border", align_corners=False) (projection.py:235-241, :266-272);
+      ``code`` = the first that applies of 1: j outside [0, F); 2: not q.z > 0; 3: not 0 <= uv < 1 in both coordinates
+      (projection.py:294-295); 0 otherwise;  ``error`` = (ẑ − q.z) / q.z where code == 0, else exactly 0 — negative: frame j's surface
+      is nearer than the point (occluded there, or inconsistent); positive: the point floats in front of j's surface.
+
+    ``depths`` (b, F, h, w); ``intrinsics`` (b, F, 3, 3); ``extrinsics`` (b, F, 4, 4) camera-to-world, or a LazyExtrinsics (its chain is
+    formed for this call only).  ``offsets``: 1 to 8 distinct non-zero ints with |d| <= F − 1, in the order of the outputs.  ``frames``:
+    None, a slice with step 1 or (first, count) over the F frames; targets outside the window but inside the video are read.
+    ``tolerance`` (None or >= 0): with it ``support`` (b, count, h, w) uint8, the number of offsets with code == 0 and
+    |error| <= tolerance.  ``details``: ``positions`` (uv), ``reprojected`` (q.z) and ``sampled`` (ẑ).  ``sums``: ``frame_sum`` = Σ|error|
+    over code == 0 and ``frame_valid`` = their count per (frame, offset), float64.  -> DepthConsistency; maps are (b, count, n_off, h, w).
+
+    ONE pass over depth (fm_depth_consistency), a small launch before it for the window's relative poses and the ordered second stage of
+    the sums after it: no (…, h, w, 3) surfaces and no F×F poses exist.  Never differentiable, and it only reads: nothing is cached or
+    noted on any tensor, no LazyExtrinsics is left evaluated, no look-ahead, tap image or optimiser state moves.  Host tensors after
+    install() go to the same composition of the reference's own functions; without install() they are refused."""
+    with torch.no_grad():
+        lazy = isinstance(extrinsics, LazyExtrinsics)
+        pose_tensor = extrinsics._rel if lazy else extrinsics
+        if not torch.is_tensor(depths) or not torch.is_tensor(intrinsics) or not torch.is_tensor(pose_tensor):
+            raise RuntimeError("flowmap_amd: depth_consistency: depths and intrinsics must be tensors, extrinsics a tensor or a LazyExtrinsics")
+        if depths.dim() != 4:
+            raise RuntimeError(f"flowmap_amd: depth_consistency: depths of shape {tuple(depths.shape)}; expected (batch, frame, height, width)")
+        b, f, h, w = depths.shape
+        if tuple(intrinsics.shape) != (b, f, 3, 3):
+            raise RuntimeError(f"flowmap_amd: depth_consistency: intrinsics of shape {tuple(intrinsics.shape)} do not match the depths {(b, f, h, w)}: "
+                               f"expected {(b, f, 3, 3)}")
+        if tuple(extrinsics.shape) != (b, f, 4, 4):
+            raise RuntimeError(f"flowmap_amd: depth_consistency: extrinsics of shape {tuple(extrinsics.shape)} do not match the depths {(b, f, h, w)}: "
+                               f"expected {(b, f, 4, 4)}")
+        for name, value in (("depths", depths), ("intrinsics", intrinsics), ("extrinsics", pose_tensor)):
+            if value.dtype != torch.float32:
+                raise RuntimeError(f"flowmap_amd: depth_consistency: {name} must be float32 (got {value.dtype})")
+        if f < 2:
+            raise ValueError("flowmap_amd: depth_consistency: a video of one frame has no other frame to compare with")
+        offsets = _check_offsets(offsets, f)
+        first, count = parse_window(frames, f, "depth_consistency", "frames")
+        if tolerance is not None and not float(tolerance) >= 0.0:
+            raise ValueError(f"flowmap_amd: depth_consistency: tolerance must be None or >= 0 (got {tolerance!r})")
+        if b * count > 65535:
+            raise ValueError(f"flowmap_amd: depth_consistency: batch x frames = {b * count} exceeds the 65 535 (batch entry, frame) rows of one call: "
+                             "ask for a window of frames")
+        dev = depths.device
+        from .. import _reference
+
+        if _reference.twins and _reference.on_host(depths):  # host tensors after install(): the reference's own functions
+            _reference.counters["host_calls"] += 1
+            ext = extrinsics.materialize().detach() if lazy else extrinsics.detach()  # (a LazyExtrinsics of host tensors is the reference's own)
+            return _consistency_on_host(_reference.twins.__getitem__, depths.detach(), intrinsics.detach(), ext, offsets, first, count,
+                                        None if tolerance is None else float(tolerance), details, sums)
+        _refuse_host("depth_consistency", dev)
+        check_device(depths, intrinsics, pose_tensor)
+        ext = extrinsics
+        if lazy:  # the chain for this call only: nothing is kept on the LazyExtrinsics or noted on the flow tensor
+            ext = ext._dense if ext._dense is not None else _ops.PoseChain.apply(ext._rel.detach())
+        k = intrinsics.detach()
+        out = _ops.depth_consistency(depths.detach(), k, _ops.intrinsics_inverse_peek(k), ext.detach(), offsets, first, count, tolerance, details, sums)
+        return DepthConsistency(*out, first, offsets)
 
 
 def focal_sweep(depths: Tensor, weights, backward_flow: Tensor, focal_length_candidates: Tensor, pairs=None, indices: Optional[Tensor] = None,

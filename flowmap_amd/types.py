@@ -9,6 +9,7 @@
   TrackResiduals  what LossTracking.residuals returns, one per segment (likewise)
   AlignmentResiduals  what ExtrinsicsProcrustes.residuals returns (likewise: the fit keeps its objective's terms to itself)
   FocalSweep  what IntrinsicsSoftmin.residuals returns (likewise: the sweep keeps its error curve and per-candidate poses to itself)
+  DepthConsistency  what projection.depth_consistency / Model.consistency return (likewise: the reference never compares its depth maps)
 
 The reference's own dataclasses are accepted everywhere these are (duck typing): the
 drop-in never checks the class, only the attribute names.
@@ -162,3 +163,30 @@ class FocalSweep:
     intrinsics: Tensor  # (batch, count, 3, 3) float32: Σ soft·K_candidate — what forward returns per frame
     poses: Optional[Tensor]  # (batch, count, n, 4, 4) float32: the fitted relative pose per candidate, later -> earlier; None unless asked for
     point_error: Optional[Tensor]  # (batch, count, n, P) float32: the per-point term before the sum; None unless asked for
+
+
+@dataclass
+class DepthConsistency:
+    """Do the depth maps agree with each other under the chained camera poses?  For the source frames [first_frame, first_frame + count),
+    every offset d of ``offsets`` (target j = i + d) and every pixel: p = unproject(xy, depth_i, K_i), q = (E_j⁻¹·E_i)·[p; 1],
+    uv = project_camera_space(q, K_j), ẑ = the bilinear, border-clamped sample of depth_j at uv (flowmap/model/projection.py:76-90, :154,
+    :49-58, :235-241) — projection.depth_consistency.  ``maps`` is (batch, count, n_off, H, W)."""
+
+    error: Tensor  # maps float32: (ẑ − q.z) / q.z where code == 0, else exactly 0; negative: frame j's surface is nearer than the point
+    code: Tensor  # maps uint8: 1 no frame j, 2 not q.z > 0, 3 not 0 <= uv < 1 (projection.py:294-295), 0 otherwise — the first that applies
+    positions: Optional[Tensor]  # maps + (2,): uv; None unless asked for (details), as the two below
+    reprojected: Optional[Tensor]  # maps: q.z
+    sampled: Optional[Tensor]  # maps: ẑ
+    support: Optional[Tensor]  # (batch, count, H, W) uint8: the offsets with code == 0 and |error| <= tolerance; None without a tolerance
+    frame_sum: Optional[Tensor]  # (batch, count, n_off) float64: Σ |error| over code == 0; None unless asked for (sums)
+    frame_valid: Optional[Tensor]  # (batch, count, n_off) float64: the number of pixels with code == 0
+    first_frame: int
+    offsets: tuple
+
+    def frame_error(self) -> Tensor:
+        """frame_sum / (frame_valid or 1): the mean |error| of each (frame, offset) over the pixels that land in the other frame."""
+        if self.frame_sum is None:
+            raise RuntimeError("flowmap_amd: DepthConsistency.frame_error needs the sums (depth_consistency(..., sums=True))")
+        from .loss.loss import or_one
+
+        return self.frame_sum / or_one(self.frame_valid)

@@ -45,8 +45,10 @@ extern "C" {
  * fm_flow_residuals / fm_flow_residual_blocks; the existing entries are unchanged; version 10: the tracking residual maps —
  * fm_track_residuals / fm_track_residual_workspace; the existing entries are unchanged; version 11: the alignment residual maps —
  * fm_alignment_residuals / fm_alignment_residual_workspace; the existing entries are unchanged; version 12: the softmin focal sweep per
- * pair — fm_focal_sweep; the existing entries are unchanged).  A binding checks fm_abi_version() == FM_ABI_VERSION when it loads the library. */
-#define FM_ABI_VERSION 12
+ * pair — fm_focal_sweep; the existing entries are unchanged; version 13: the depth consistency across frame offsets —
+ * fm_depth_consistency / fm_depth_consistency_blocks; the existing entries are unchanged).  A binding checks
+ * fm_abi_version() == FM_ABI_VERSION when it loads the library. */
+#define FM_ABI_VERSION 13
 int fm_abi_version(void);
 
 #define FM_STAT_STRIDE 16      /* doubles per pair in `stats` */
@@ -851,6 +853,44 @@ int fm_focal_sweep(const float* depth, const float* weights, float weight_sensit
                    const float* focal_lengths, const float* candidate_k, const float* candidate_kinv, int batch, int frames, int height, int width,
                    int first_pair, int count, int candidates, double* error, float* soft, float* focal, float* intrinsics, float* poses,
                    float* point_error, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Depth consistency across frame offsets (ABI version 13).  Do the depth maps agree with each other under the chained camera poses, a
+ * few frames apart?  For batch entry b, source frame i of the window, offset d = offsets[o] != 0, target j = i + d and the pixel with
+ * centre xy (sample_image_grid, flowmap/model/projection.py:93-113):
+ *   p = unproject(xy, depth_i, K_i) (projection.py:76-90);  q = (E_j⁻¹·E_i)·[p; 1], xyz — the relative transformation of
+ *   compute_forward_flow / compute_track_flow (projection.py:154, :288) at distance d;  uv = project_camera_space(q, K_j)
+ *   (projection.py:49-58, its ε = 1e-5 and ±1e8 / NaN clamp);  ẑ = grid_sample(depth_j, uv·2−1, bilinear, border,
+ *   align_corners=False) (projection.py:235-241, :266-272);
+ *   code = 1: j outside [0, F);  2: not q.z > 0;  3: not 0 <= uv < 1 in both coordinates (projection.py:294-295);  0 otherwise — the
+ *   first that applies;  error = (ẑ − q.z)/q.z where code == 0, else exactly 0 (fm_math.h: depth_consistency_at).
+ * ONE pass over depth plus two small launches: nothing of size (B,F,H,W,3) and no F×F pose table is formed.
+ *
+ *   depth (B,F,H,W), k, kinv (B,F,3,3), ext (B,F,4,4) camera-to-world: all dense, the WHOLE stacks — targets outside the window are read.
+ *   offsets (n_offsets) HOST int32: 1 <= n_offsets <= 8 distinct non-zero values with |d| <= F - 1, in the order of the outputs.
+ *   first_frame, count: the source frames [first_frame, first_frame + count) of every batch entry, 0 <= first_frame, count >= 1,
+ *     first_frame + count <= F, B·count <= 65535.  H·W < 2^30.
+ *   error (B,count,n_offsets,H,W) out; code (same shape) bytes out.
+ *   positions (B,count,n_offsets,H,W,2), reprojected, sampled (B,count,n_offsets,H,W) out, or all three NULL: uv, q.z and ẑ — as
+ *     computed where code is 2 or 3, 0 where it is 1.
+ *   support (B,count,H,W) bytes out or NULL: the number of offsets with code == 0 and |error| <= tolerance (tolerance >= 0).
+ *   frame_sum, frame_valid (B,count,n_offsets) doubles out, or both NULL: Σ (double)|error| over code == 0 and the number of such
+ *     pixels, in fp64 from the pixel upward WITHOUT atomics: every workgroup leaves its partials in `workspace` —
+ *     (B,count,n_offsets,blocks,2) doubles, blocks from fm_depth_consistency_blocks, 16-byte aligned, contents unspecified on entry
+ *     and on return — and a second small launch adds a row's partials in ascending workgroup order.  Which pixels a workgroup owns
+ *     depends on (H, W) only: the sums are bit-reproducible, and bit-identical whether a frame is reached through the full range, a
+ *     window or another batch.
+ *   rel (B,count,n_offsets,16) floats: scratch — the first launch leaves E_j⁻¹·E_i of every row there (rel[15] = 0: no such target).
+ * EVERY element of every output is written (no zero fill beforehand).  One thread per four adjacent pixels, looping over the offsets;
+ * 16-byte loads / stores of the float maps and 4-byte stores of the byte maps when W % 4 == 0 and the bases are aligned, else a
+ * scalar path with the same results.
+ *
+ * fm_depth_consistency_blocks: blocks[0] (HOST int) = workgroups per (batch entry, source frame) at this image size. */
+int fm_depth_consistency_blocks(int height, int width, int* blocks);
+int fm_depth_consistency(const float* depth, const float* k, const float* kinv, const float* ext, const int32_t* offsets, int n_offsets,
+                         int batch, int frames, int height, int width, int first_frame, int count, float tolerance, float* error,
+                         uint8_t* code, float* positions, float* reprojected, float* sampled, uint8_t* support, double* frame_sum,
+                         double* frame_valid, float* rel, double* workspace, void* stream);
 
 #ifdef __cplusplus
 }
