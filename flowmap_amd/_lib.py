@@ -125,6 +125,8 @@ SIGNATURES = {
     "fm_focal_sweep": [P, P, F, P, P, L, P, P, P, I, I, I, I, I, I, I] + [P] * 7,
     "fm_depth_consistency_blocks": [I, I, P],
     "fm_depth_consistency": [P] * 5 + [I] * 7 + [F] + [P] * 11,
+    "fm_render_views_workspace": [I, I, I, I, I, P],
+    "fm_render_views": [P] * 7 + [I] * 9 + [F, F] + [P] * 5,
 }
 
 _lib: Optional[ctypes.CDLL] = None

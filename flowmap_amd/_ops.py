@@ -242,7 +242,7 @@ def _dense_flow_is_rough(bwd_flow: Tensor, h: int, w: int) -> bool:
 # which backward path the facades selected (tests)
 counters = {"procrustes_planned": 0, "procrustes_dense_planned": 0, "flow_packs": 0, "flow_packs_bitmask": 0, "procrustes_plans_built": 0, "track_tap_samples": 0,
             "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0, "flow_residuals": 0, "track_residuals": 0, "alignment_residuals": 0, "focal_sweep": 0,
-            "depth_consistency": 0}
+            "depth_consistency": 0, "render_views": 0}
 
 
 class LeadingFrames:
@@ -876,6 +876,17 @@ def depth_consistency(depth, k, kinv, ext, offsets, first_frame, count, toleranc
                                         -1.0 if tolerance is None else float(tolerance), bool(details), bool(sums))
     counters["depth_consistency"] += 1
     return tuple(x if x.numel() else None for x in out)
+
+
+def render_views(depth, kinv, ext, colors, view_k, view_ext, pairs, shape, radius, near, background):
+    """The source frames of ``pairs`` — (n_pairs, 2) int32 on the tensors' device: (view, source frame) — splatted into the cameras
+    ``view_k`` / ``view_ext`` at the output ``shape`` (csrc/fm_torch.cpp: render_views_op -> fm_render_views): (color, depth, source),
+    color None without ``colors``.  The z-buffer set to all-ones, a small launch for the pairs' relative poses, one pass over the pairs'
+    depth with 64-bit atomic minima, one resolve pass.  Reads its arguments and nothing else."""
+    color, out_depth, source = torch_ops().render_views(depth, kinv, ext, colors, view_k, view_ext, pairs, int(shape[0]), int(shape[1]), int(radius),
+                                                        float(near), float(background))
+    counters["render_views"] += 1
+    return (color if colors is not None else None), out_depth, source
 
 
 def softmin_intrinsics(depth, weights, bwd_flow, indices, candidate_k, rel, weight_sens, frames):

@@ -546,6 +546,58 @@ FM_HD DepthConsistencyTerm depth_consistency_at(const float ray[3], float z, con
 }
 
 // ---------------------------------------------------------------------------------
+// The splat of ONE source pixel into ONE view (projection.render_views; fm_render_views.hip and its host twin both call this):
+//   p = z·K_i⁻¹[u,v,1] (`ray` is K_i⁻¹[u,v,1]),  q = (E_v⁻¹E_i)·[p;1],  uv = project_camera_space(q, K_v) (ε = 1e-5, clamp),
+//   live = q.z > near (near >= 0) and 0 <= uv < 1 in both coordinates,  bin (tx, ty) = (floor(u·ow), floor(v·oh)) — clamped into the
+//   image: u < 1 may still round to u·ow == ow,
+//   key = float_bits(q.z) << 32 | index: q.z > 0, so the bit pattern orders as the value, and among equal q.z the lower index wins.
+// A live key is below kRenderHole (its upper word is at most +inf's 0x7f800000), the value the z-buffer is filled with.
+// ---------------------------------------------------------------------------------
+constexpr unsigned long long kRenderHole = ~0ULL;
+
+struct RenderSplat {
+  float u, v, qz;
+  int tx, ty;
+  bool live;
+};
+
+FM_HD unsigned long long render_key(float qz, unsigned int index) {
+  return ((unsigned long long)__builtin_bit_cast(unsigned int, qz) << 32) | (unsigned long long)index;
+}
+
+FM_HD RenderSplat render_splat_at(const float ray[3], float z, const Pose& rel, const Mat3& kv, float near, int oh, int ow) {
+  float p[3], q[3];
+  p[0] = ray[0] * z;
+  p[1] = ray[1] * z;
+  p[2] = ray[2] * z;
+  apply_pose(rel, p, q);
+  const Projected pr = project_point(q, kv);
+  RenderSplat o;
+  o.u = pr.u;
+  o.v = pr.v;
+  o.qz = q[2];
+  o.live = q[2] > near && pr.u >= 0.f && pr.u < 1.f && pr.v >= 0.f && pr.v < 1.f;
+  const int tx = o.live ? (int)floorf(pr.u * (float)ow) : 0, ty = o.live ? (int)floorf(pr.v * (float)oh) : 0;
+  o.tx = tx < ow - 1 ? tx : ow - 1;
+  o.ty = ty < oh - 1 ? ty : oh - 1;
+  return o;
+}
+
+// The (2r+1)² target pixels around a live splat's bin that lie inside the (oh, ow) image: fn(y·ow + x) for each.
+template <typename Fn>
+FM_HD void render_footprint(const RenderSplat& s, int radius, int oh, int ow, Fn fn) {
+  for (int dy = -radius; dy <= radius; ++dy) {
+    const int y = s.ty + dy;
+    if (y < 0 || y >= oh) continue;
+    for (int dx = -radius; dx <= radius; ++dx) {
+      const int x = s.tx + dx;
+      if (x < 0 || x >= ow) continue;
+      fn((size_t)y * ow + x);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------
 // One (candidate, sampled pixel) term of IntrinsicsSoftmin's score (intrinsics_softmin.py:105-121):
 //   X = z·K⁻¹[u,v,1] (unproject the later frame's pixel), X' = T·X (fitted pose, later -> earlier),
 //   xy = project_camera_space(X', K) (exact ±1e8 / NaN->0 semantics), flow = xy − (u,v),
@@ -1362,4 +1414,5 @@ FM_HD void dense_bwd_s(const DenseBwd& c, const float h[3], const float t[3], co
 #include "fm_alignment_residuals_host.h"
 #include "fm_focal_sweep_host.h"
 #include "fm_depth_consistency_host.h"
+#include "fm_render_views_host.h"
 #endif

@@ -1,5 +1,5 @@
 // Argument checks and size formulas of the residual entry points (include/flowmap_hip.h: fm_flow_residuals, fm_track_residuals,
-// fm_alignment_residuals, fm_focal_sweep, fm_depth_consistency and their size functions), stated ONCE: the device build (fm_*.hip) and the serial host build of
+// fm_alignment_residuals, fm_focal_sweep, fm_depth_consistency, fm_render_views and their size functions), stated ONCE: the device build (fm_*.hip) and the serial host build of
 // the same ABI (fm_*_host.h) both call these, so the two refuse the same calls and size the same workspaces.  Plain C++, no HIP.
 // Device-only, and therefore not here: the 16-byte path's eligibility and the pointer alignment the kernels need (the host build reads
 // element by element and never touches the workspace).
@@ -131,6 +131,37 @@ static inline bool depth_consistency_args_ok(const float* depth, const float* k,
       if (offsets[j] == offsets[i]) return false;
   }
   return true;
+}
+
+// ---- rendered views ----
+constexpr int kRenderTile = 1024;        // source pixels per workgroup of render_splat_kernel
+constexpr int kRenderMaxRadius = 2;      // a splat covers (2r+1)² target pixels
+constexpr long kRenderMaxSources = 1L << 31;  // `source` is int32: frames x height x width stays below this
+static inline long render_blocks(long pixels) { return (pixels + kRenderTile - 1) / kRenderTile; }
+// bytes of workspace: the (B,V,OH,OW) 64-bit z-buffer, then one 16-float pose row per (batch entry, pair)
+static inline long render_views_key_bytes(long batch, long views, long out_pixels) { return 8 * batch * views * out_pixels; }
+static inline long render_views_workspace_bytes(long batch, long views, long out_pixels, long n_pairs) {
+  return render_views_key_bytes(batch, views, out_pixels) + 64 * batch * n_pairs;
+}
+static inline bool render_views_shape_ok(int batch, int views, int out_height, int out_width, int n_pairs) {
+  if (!(batch >= 1 && views >= 1 && n_pairs >= 0 && res_frame_ok(out_height, out_width))) return false;
+  if ((long)batch * n_pairs > kResMaxRows) return false;
+  return (long)batch * views <= (1L << 37) / ((long)out_height * out_width);  // (one resolve thread per target pixel: a grid dimension)
+}
+static inline bool render_views_workspace_args_ok(int batch, int views, int out_height, int out_width, int n_pairs, const long* bytes) {
+  return bytes && render_views_shape_ok(batch, views, out_height, out_width, n_pairs);
+}
+
+static inline bool render_views_args_ok(const float* depth, const float* kinv, const float* ext, const float* colors, const float* view_k,
+                                        const float* view_ext, const int32_t* pairs, int n_pairs, int batch, int frames, int height, int width, int views,
+                                        int out_height, int out_width, int radius, float near, float background, const float* color, const float* out_depth,
+                                        const int32_t* source, const void* workspace) {
+  if (!(depth && kinv && ext && view_k && view_ext && out_depth && source && workspace)) return false;
+  if ((colors != nullptr) != (color != nullptr)) return false;
+  if (!render_views_shape_ok(batch, views, out_height, out_width, n_pairs) || (n_pairs > 0 && !pairs)) return false;
+  if (!(frames >= 1 && res_frame_ok(height, width) && (long)frames * height * width < kRenderMaxSources)) return false;
+  if (radius < 0 || radius > kRenderMaxRadius) return false;
+  return near >= 0.f && near < __builtin_inff() && background == background;
 }
 
 }  // namespace fm

@@ -51,7 +51,7 @@ using OptTensor = std::optional<Tensor>;
   X(fm_adam_step_capturable) X(fm_softmin_score_fwd) X(fm_softmin_score_bwd) X(fm_softmin_blend_fwd) X(fm_softmin_blend_bwd)         \
   X(fm_random_subset) X(fm_random_subset_stateful) X(fm_abi_version) X(fm_flow_loss_fused_taps) X(fm_track_loss_fused_fwd_taps) X(fm_tap_grad_apply) \
   X(fm_flow_loss_fused_bitmask) X(fm_flow_residuals) X(fm_flow_residual_blocks) X(fm_track_residuals) X(fm_track_residual_workspace) \
-  X(fm_depth_consistency) X(fm_depth_consistency_blocks)
+  X(fm_depth_consistency) X(fm_depth_consistency_blocks) X(fm_render_views) X(fm_render_views_workspace)
 
 struct Api {
 #define X(name) decltype(&::name) name = nullptr;
@@ -1681,6 +1681,47 @@ static std::vector<Tensor> depth_consistency_op(const Tensor& depth_in, const Te
   return {error, code, positions, reprojected, sampled, support, frame_sum, frame_valid};
 }
 
+// projection.render_views (fm_render_views): the depth maps of the pairs' source frames splatted into the views' cameras with a 64-bit
+// z-buffer of atomic minima, then resolved.  `pairs` (n_pairs, 2) int32: (view, source frame).  Not differentiable.
+// -> {color (empty without colors), depth, source}.  The z-buffer and the pose rows are this call's only scratch.
+static std::vector<Tensor> render_views_op(const Tensor& depth_in, const Tensor& kinv_in, const Tensor& ext_in, const OptTensor& colors_in, const Tensor& view_k_in,
+                                           const Tensor& view_ext_in, const Tensor& pairs_in, int64_t out_h, int64_t out_w, int64_t radius, double near,
+                                           double background) {
+  at::NoGradGuard no_grad;
+  const bool has_colors = colors_in.has_value() && colors_in->defined();
+  const Tensor colors_t = has_colors ? *colors_in : Tensor();
+  const auto dev = check_device({&depth_in, &kinv_in, &ext_in, &colors_t, &view_k_in, &view_ext_in, &pairs_in});
+  const Tensor depth = f32c(depth_in.detach(), "depth"), kinv = f32c(kinv_in.detach(), "inverse intrinsics"), ext = f32c(ext_in.detach(), "extrinsics"),
+               view_k = f32c(view_k_in.detach(), "view intrinsics"), view_ext = f32c(view_ext_in.detach(), "view extrinsics");
+  const Tensor colors = has_colors ? f32c(colors_t.detach(), "colors") : Tensor();
+  TORCH_CHECK(pairs_in.scalar_type() == at::kInt && pairs_in.dim() == 2 && pairs_in.size(1) == 2, "flowmap_amd: pairs must be (n_pairs, 2) int32");
+  const Tensor pairs = pairs_in.contiguous();
+  TORCH_CHECK(depth.dim() == 4, "flowmap_amd: depth must be (batch, frame, height, width)");
+  const int64_t b = depth.size(0), f = depth.size(1), h = depth.size(2), w = depth.size(3), n_pairs = pairs.size(0);
+  TORCH_CHECK(view_k.dim() == 4 && view_k.size(0) == b, "flowmap_amd: view intrinsics must be (batch, view, 3, 3)");
+  const int64_t v = view_k.size(1);
+  TORCH_CHECK(h * w < (int64_t(1) << 30) && f * h * w < (int64_t(1) << 31), "flowmap_amd: render_views indexes source pixels with int32: frames x height x width = ",
+              f * h * w, " must stay below 2^31");
+  TORCH_CHECK(kinv.sizes() == at::IntArrayRef({b, f, 3, 3}) && ext.sizes() == at::IntArrayRef({b, f, 4, 4}), "flowmap_amd: intrinsics / extrinsics shapes do not match depth");
+  TORCH_CHECK(v >= 1 && view_k.sizes() == at::IntArrayRef({b, v, 3, 3}) && view_ext.sizes() == at::IntArrayRef({b, v, 4, 4}),
+              "flowmap_amd: view intrinsics / extrinsics must be (batch, view, 3, 3) and (batch, view, 4, 4)");
+  TORCH_CHECK(!has_colors || colors.sizes() == at::IntArrayRef({b, f, 3, h, w}), "flowmap_amd: colors must be (batch, frame, 3, height, width)");
+  TORCH_CHECK(out_h >= 1 && out_w >= 1 && out_h * out_w < (int64_t(1) << 30) && b * v <= (int64_t(1) << 37) / (out_h * out_w),
+              "flowmap_amd: render_views: the output shape (", out_h, ", ", out_w, ") x ", b * v, " views is out of range");
+  TORCH_CHECK(b * n_pairs <= 65535, "flowmap_amd: render_views handles at most 65 535 (batch entry, view, source) rows per call (got ", b * n_pairs, "): split the views");
+  long bytes = 0;
+  FM_CALL(fm_render_views_workspace, (int)b, (int)v, (int)out_h, (int)out_w, (int)n_pairs, &bytes);
+  const auto fopt = depth.options();
+  Tensor work = at::empty({((int64_t)bytes + 7) / 8}, fopt.dtype(at::kLong));
+  Tensor color = has_colors ? at::empty({b, v, 3, out_h, out_w}, fopt) : at::empty({0}, fopt);
+  Tensor out_depth = at::empty({b, v, out_h, out_w}, fopt), source = at::empty({b, v, out_h, out_w}, fopt.dtype(at::kInt));
+  DeviceScope scope(dev);
+  FM_CALL(fm_render_views, ptr(depth), ptr(kinv), ptr(ext), has_colors ? ptr(colors) : nullptr, ptr(view_k), ptr(view_ext), n_pairs ? ptr<int32_t>(pairs) : nullptr,
+          (int)n_pairs, (int)b, (int)f, (int)h, (int)w, (int)v, (int)out_h, (int)out_w, (int)radius, (float)near, (float)background,
+          has_colors ? ptr(color) : nullptr, ptr(out_depth), ptr<int32_t>(source), work.data_ptr(), scope.stream);
+  return {color, out_depth, source};
+}
+
 }  // namespace fmt
 
 TORCH_LIBRARY(flowmap_amd, m) {
@@ -1765,4 +1806,7 @@ TORCH_LIBRARY(flowmap_amd, m) {
   m.def("depth_consistency(Tensor depth, Tensor k, Tensor kinv, Tensor ext, int[] offsets, int first_frame, int count, float tolerance, bool details, "
         "bool sums) -> Tensor[]",
         fmt::depth_consistency_op);
+  m.def("render_views(Tensor depth, Tensor kinv, Tensor ext, Tensor? colors, Tensor view_k, Tensor view_ext, Tensor pairs, int out_h, int out_w, int radius, "
+        "float near, float background) -> Tensor[]",
+        fmt::render_views_op);
 }

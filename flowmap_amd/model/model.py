@@ -20,7 +20,7 @@ from ..types import ModelOutput
 from .backbone import BackboneExplicitDepth, BackboneExplicitDepthCfg  # noqa: F401  (flowmap/model/backbone/backbone_explicit_depth.py)
 from .extrinsics_procrustes import ExtrinsicsProcrustes, ExtrinsicsProcrustesCfg
 from .extrinsics_regressed import ExtrinsicsRegressed, ExtrinsicsRegressedCfg
-from .projection import depth_consistency, sample_image_grid, unproject
+from .projection import depth_consistency, render_views, sample_image_grid, unproject
 
 
 _K_CONSTANTS: dict = {}
@@ -128,3 +128,10 @@ class Model(nn.Module):
         """projection.depth_consistency of a ModelOutput's depths under its intrinsics and extrinsics (``offsets``, ``frames``,
         ``tolerance``, ``details``, ``sums`` as there) -> DepthConsistency.  It only reads: a LazyExtrinsics stays unevaluated."""
         return depth_consistency(model_output.depths, model_output.intrinsics, model_output.extrinsics, **kw)
+
+    def render(self, model_output, batch=None, **kw):
+        """projection.render_views of a ModelOutput's depths under its intrinsics and extrinsics, coloured with ``batch.videos`` when a
+        batch is given (``views`` / ``sources`` or ``held_out`` / ``offsets``, ``shape``, ``radius``, ``near``, ``background`` as there)
+        -> RenderedViews.  It only reads: a LazyExtrinsics stays unevaluated."""
+        colors = None if batch is None else batch.videos
+        return render_views(model_output.depths, model_output.intrinsics, model_output.extrinsics, colors, **kw)

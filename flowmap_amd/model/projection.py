@@ -24,7 +24,7 @@ from torch import Tensor
 from .. import _ops
 from .._base import parse_window
 from .._lib import check_device, using_test_double
-from ..types import AlignmentResiduals, DepthConsistency, FocalSweep
+from ..types import AlignmentResiduals, DepthConsistency, FocalSweep, RenderedViews
 
 # --------------------------------------------------------------------------------------
 # small tensor helpers (no kernels needed: pure indexing / concatenation)
@@ -630,17 +630,17 @@ def alignment_residuals(surfaces, backward_flows: Tensor, backward_weights, extr
         return AlignmentResiduals(*out, first)
 
 
-def _check_offsets(offsets, frames: int) -> tuple:
+def _check_offsets(offsets, frames: int, what: str = "depth_consistency") -> tuple:
     is_int = lambda x: isinstance(x, int) and not isinstance(x, bool)  # noqa: E731
     if not isinstance(offsets, (tuple, list)) or not all(is_int(d) for d in offsets):
-        raise ValueError(f"flowmap_amd: depth_consistency: offsets must be a tuple or list of ints, got {offsets!r}")
+        raise ValueError(f"flowmap_amd: {what}: offsets must be a tuple or list of ints, got {offsets!r}")
     offsets = tuple(int(d) for d in offsets)
     if not 1 <= len(offsets) <= 8:
-        raise ValueError(f"flowmap_amd: depth_consistency: between 1 and 8 offsets per call (got {len(offsets)})")
+        raise ValueError(f"flowmap_amd: {what}: between 1 and 8 offsets per call (got {len(offsets)})")
     if 0 in offsets or len(set(offsets)) != len(offsets):
-        raise ValueError(f"flowmap_amd: depth_consistency: offsets must be distinct and non-zero, got {offsets}")
+        raise ValueError(f"flowmap_amd: {what}: offsets must be distinct and non-zero, got {offsets}")
     if any(abs(d) > frames - 1 for d in offsets):
-        raise ValueError(f"flowmap_amd: depth_consistency: offsets {offsets} reach past the {frames} frames of the video (|d| <= {frames - 1})")
+        raise ValueError(f"flowmap_amd: {what}: offsets {offsets} reach past the {frames} frames of the video (|d| <= {frames - 1})")
     return offsets
 
 
@@ -744,6 +744,161 @@ def depth_consistency(depths: Tensor, intrinsics: Tensor, extrinsics, offsets=(-
         k = intrinsics.detach()
         out = _ops.depth_consistency(depths.detach(), k, _ops.intrinsics_inverse_peek(k), ext.detach(), offsets, first, count, tolerance, details, sums)
         return DepthConsistency(*out, first, offsets)
+
+
+def _render_on_host(ref, depths, intrinsics, extrinsics, colors, view_k, view_ext, pairs, shape, radius, near, background):
+    """Host tensors after install(): the same composition from the reference's own functions (``ref``: name -> original), an int64 key
+    per candidate and scatter_reduce_(amin) -> (color, depth, source)."""
+    b, f, h, w = depths.shape
+    oh, ow = shape
+    v = view_k.shape[1]
+    xy, _ = ref("sample_image_grid")((h, w), depths.device)
+    hole = torch.iinfo(torch.int64).max
+    zbuf = torch.full((b, v, oh * ow), hole, dtype=torch.int64)
+    index = torch.arange(h * w, dtype=torch.int64)
+    for view, src in pairs:
+        points = ref("unproject")(xy, depths[:, src], intrinsics[:, src][:, None, None])
+        rel = (view_ext[:, view].double().inverse() @ extrinsics[:, src].double()).float()
+        q = ref("transform_rigid")(ref("homogenize_points")(points), rel[:, None, None])[..., :3]
+        uv = ref("project_camera_space")(q, view_k[:, view][:, None, None])
+        qz = q[..., 2].contiguous()
+        live = ((qz > near) & (uv >= 0).all(dim=-1) & (uv < 1).all(dim=-1)).reshape(b, h * w)
+        tx = torch.floor(uv[..., 0] * ow).clamp(0, ow - 1).long().reshape(b, h * w)
+        ty = torch.floor(uv[..., 1] * oh).clamp(0, oh - 1).long().reshape(b, h * w)
+        key = (qz.view(torch.int32).long().reshape(b, h * w) << 32) | (src * h * w + index)
+        for dy in range(-radius, radius + 1):
+            for dx in range(-radius, radius + 1):
+                x, y = tx + dx, ty + dy
+                ok = live & (x >= 0) & (x < ow) & (y >= 0) & (y < oh)
+                at = torch.where(ok, y * ow + x, torch.zeros_like(x))
+                zbuf[:, view].scatter_reduce_(1, at, torch.where(ok, key, torch.full_like(key, hole)), "amin")
+    holes = zbuf == hole
+    winner = torch.where(holes, torch.zeros_like(zbuf), zbuf & 0xFFFFFFFF)
+    source = torch.where(holes, torch.full_like(zbuf, -1), winner).to(torch.int32).reshape(b, v, oh, ow)
+    depth = torch.where(holes, torch.zeros_like(zbuf), zbuf >> 32).to(torch.int32).view(torch.float32).reshape(b, v, oh, ow)
+    color = None
+    if colors is not None:
+        planes = colors.permute(0, 2, 1, 3, 4).reshape(b, 3, 1, f * h * w).expand(b, 3, v, f * h * w)
+        color = torch.gather(planes, 3, winner[:, None].expand(b, 3, v, oh * ow))
+        color = torch.where(holes[:, None], torch.full_like(color, background), color).permute(0, 2, 1, 3).reshape(b, v, 3, oh, ow).contiguous()
+    return color, depth, source
+
+
+def render_views(depths: Tensor, intrinsics: Tensor, extrinsics, colors: Optional[Tensor] = None, *, views=None, sources=None, held_out=None,
+                 offsets=(-2, -1, 1, 2), shape=None, radius: int = 0, near: float = 0.0, background: float = 0.0) -> RenderedViews:
+    """What does the reconstruction look like from a camera?  The depth maps of some source frames are splatted into each view with a
+    z-buffer — a forward warp.  For a view v (camera K_v, E_v, output shape (oh, ow)), a source frame i of its list and the pixel of
+    frame i with centre xy (``sample_image_grid``):
+
+      p = unproject(xy, depth_i, K_i);  q = (E_v⁻¹·E_i)·[p; 1], the relative pose formed in fp64 and rounded once;
+      uv = project_camera_space(q, K_v) (the reference's ε = 1e-5 and clamp);  the point is live when q.z > ``near`` and 0 <= uv < 1 in
+      both coordinates;  its bin is (floor(u·ow), floor(v·oh));  with ``radius`` r in {0, 1, 2} it covers the (2r+1)² pixels around the
+      bin that lie inside the image.  A target pixel keeps the candidate with the smallest q.z, among equal q.z the lower absolute source
+      index i·h·w + y·w + x: the result depends on the set of candidates only and is bit-reproducible.
+
+    ``depths`` (b, F, h, w); ``intrinsics`` (b, F, 3, 3); ``extrinsics`` (b, F, 4, 4) camera-to-world, or a LazyExtrinsics (its chain is
+    formed for this call only); ``colors`` (b, F, 3, h, w) or None.  Exactly one of:
+
+      ``views`` = (K_v (b, V, 3, 3), E_v (b, V, 4, 4)): free cameras, every one rendered from the frames ``sources`` — None (all), a
+      slice with step 1 or (first, count) over the F frames;
+      ``held_out`` = a slice with step 1 (``slice(None)``: every frame) or (first, count) over the F frames: view v is frame j's own K_j,
+      E_j, rendered from the frames j + d, d in ``offsets`` (1 to 8 distinct non-zero ints), that exist — never from frame j itself.
+      ``psnr(videos[:, window])`` of the result is the held-out score.
+
+    ``shape`` defaults to (h, w).  A view with no source is all holes.  -> RenderedViews: ``source`` int32 (−1: hole), ``depth`` (the
+    winner's q.z, 0 in a hole), ``color`` (the winner's colour bit for bit, ``background`` in a hole; None without ``colors``).
+
+    Known limits.  A one-pixel splat leaves holes when the target grid is finer than the source's (or a surface is seen at a grazing
+    angle); ``radius`` trades holes for fattened silhouettes.  Background can show through the gaps of a foreground surface: a point
+    splat knows nothing of the surface between its neighbours.  F·h·w must stay below 2³¹ (``source`` is int32).
+
+    One pass over the sources' depth with 64-bit atomic minima, then one resolve pass (fm_render_views): no point cloud, no key tensor
+    per (view, source) exists.  Never differentiable, and it only reads: nothing is cached or noted on any tensor, no LazyExtrinsics
+    is left evaluated.  Host tensors after install() go to the same composition of the reference's own functions; without install()
+    they are refused."""
+    what = "render_views"
+    with torch.no_grad():
+        lazy = isinstance(extrinsics, LazyExtrinsics)
+        pose_tensor = extrinsics._rel if lazy else extrinsics
+        if not torch.is_tensor(depths) or not torch.is_tensor(intrinsics) or not torch.is_tensor(pose_tensor):
+            raise RuntimeError(f"flowmap_amd: {what}: depths and intrinsics must be tensors, extrinsics a tensor or a LazyExtrinsics")
+        if depths.dim() != 4:
+            raise RuntimeError(f"flowmap_amd: {what}: depths of shape {tuple(depths.shape)}; expected (batch, frame, height, width)")
+        b, f, h, w = depths.shape
+        if tuple(intrinsics.shape) != (b, f, 3, 3):
+            raise RuntimeError(f"flowmap_amd: {what}: intrinsics of shape {tuple(intrinsics.shape)} do not match the depths {(b, f, h, w)}: expected {(b, f, 3, 3)}")
+        if tuple(extrinsics.shape) != (b, f, 4, 4):
+            raise RuntimeError(f"flowmap_amd: {what}: extrinsics of shape {tuple(extrinsics.shape)} do not match the depths {(b, f, h, w)}: expected {(b, f, 4, 4)}")
+        if colors is not None and (not torch.is_tensor(colors) or tuple(colors.shape) != (b, f, 3, h, w)):
+            raise RuntimeError(f"flowmap_amd: {what}: colors of shape {tuple(getattr(colors, 'shape', ()))} do not match the depths {(b, f, h, w)}: "
+                               f"expected {(b, f, 3, h, w)}")
+        if (views is None) == (held_out is None):
+            raise ValueError(f"flowmap_amd: {what}: give exactly one of views=(K_v, E_v) and held_out=<a window of frames>")
+        tensors = [("depths", depths), ("intrinsics", intrinsics), ("extrinsics", pose_tensor)] + ([("colors", colors)] if colors is not None else [])
+        first_frame = kept_offsets = None
+        if views is not None:
+            if not isinstance(views, (tuple, list)) or len(views) != 2 or not all(torch.is_tensor(x) for x in views):
+                raise ValueError(f"flowmap_amd: {what}: views must be a pair of tensors (K_v (b, V, 3, 3), E_v (b, V, 4, 4))")
+            view_k, view_ext = views
+            n_views = view_k.shape[1] if view_k.dim() == 4 else 0
+            if n_views < 1 or tuple(view_k.shape) != (b, n_views, 3, 3) or tuple(view_ext.shape) != (b, n_views, 4, 4):
+                raise RuntimeError(f"flowmap_amd: {what}: views of shapes {tuple(view_k.shape)} and {tuple(view_ext.shape)}; expected (b, V, 3, 3) and "
+                                   f"(b, V, 4, 4) with b = {b}")
+            tensors += [("views[0]", view_k), ("views[1]", view_ext)]
+            first_source, n_sources = parse_window(sources, f, what, "frames")
+            pairs = [(v, i) for v in range(n_views) for i in range(first_source, first_source + n_sources)]
+        else:
+            if sources is not None:
+                raise ValueError(f"flowmap_amd: {what}: sources goes with views=; a held-out view is rendered from the frames at its offsets")
+            kept_offsets = _check_offsets(offsets, f, what)
+            first_frame, n_views = parse_window(held_out, f, what, "frames")
+            pairs = [(v, first_frame + v + d) for v in range(n_views) for d in kept_offsets if 0 <= first_frame + v + d < f]
+            view_k = view_ext = None
+        for name, value in tensors:
+            if value.dtype != torch.float32:
+                raise RuntimeError(f"flowmap_amd: {what}: {name} must be float32 (got {value.dtype})")
+        is_int = lambda x: isinstance(x, int) and not isinstance(x, bool)  # noqa: E731
+        if shape is None:
+            shape = (h, w)
+        if not isinstance(shape, (tuple, list)) or len(shape) != 2 or not all(is_int(x) and x >= 1 for x in shape):
+            raise ValueError(f"flowmap_amd: {what}: shape must be (height, width) of the output, positive ints, got {shape!r}")
+        shape = (int(shape[0]), int(shape[1]))
+        if not is_int(radius) or not 0 <= radius <= 2:
+            raise ValueError(f"flowmap_amd: {what}: radius must be 0, 1 or 2 (got {radius!r})")
+        if not (isinstance(near, (int, float)) and 0.0 <= float(near) < float("inf")):
+            raise ValueError(f"flowmap_amd: {what}: near must be a finite number >= 0 (got {near!r})")
+        if not (isinstance(background, (int, float)) and float(background) == float(background)):
+            raise ValueError(f"flowmap_amd: {what}: background must be a number (got {background!r})")
+        if f * h * w >= 2**31:
+            raise ValueError(f"flowmap_amd: {what}: frames x height x width = {f * h * w} does not fit the int32 source index (below 2^31): render a "
+                             "window of the video")
+        if b * len(pairs) > 65535:
+            raise ValueError(f"flowmap_amd: {what}: batch x (view, source) pairs = {b * len(pairs)} exceeds the 65 535 rows of one call: ask for fewer views "
+                             "or sources")
+        dev = depths.device
+        from .. import _reference
+
+        held = slice(first_frame, first_frame + n_views) if views is None else None
+        if _reference.twins and _reference.on_host(depths):  # host tensors after install(): the reference's own functions
+            _reference.counters["host_calls"] += 1
+            ext = extrinsics.materialize().detach() if lazy else extrinsics.detach()
+            if views is None:
+                view_k, view_ext = intrinsics[:, held], ext[:, held]
+            out = _render_on_host(_reference.twins.__getitem__, depths.detach(), intrinsics.detach(), ext, None if colors is None else colors.detach(),
+                                  view_k.detach(), view_ext.detach(), pairs, shape, radius, float(near), float(background))
+            return RenderedViews(*out, (h, w), first_frame, kept_offsets)
+        _refuse_host(what, dev)
+        check_device(*(value for _, value in tensors))
+        ext = extrinsics
+        if lazy:  # the chain for this call only: nothing is kept on the LazyExtrinsics or noted on the flow tensor
+            ext = ext._dense if ext._dense is not None else _ops.PoseChain.apply(ext._rel.detach())
+        ext, k = ext.detach(), intrinsics.detach()
+        if views is None:
+            view_k, view_ext = k[:, held], ext[:, held]
+        pair_tensor = torch.tensor(pairs, dtype=torch.int32).reshape(-1, 2).to(dev)
+        out = _ops.render_views(depths.detach(), _ops.intrinsics_inverse_peek(k), ext, None if colors is None else colors.detach(), view_k.detach(),
+                                view_ext.detach(), pair_tensor, shape, radius, near, background)
+        return RenderedViews(*out, (h, w), first_frame, kept_offsets)
 
 
 def focal_sweep(depths: Tensor, weights, backward_flow: Tensor, focal_length_candidates: Tensor, pairs=None, indices: Optional[Tensor] = None,

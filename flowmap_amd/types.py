@@ -10,6 +10,7 @@
   AlignmentResiduals  what ExtrinsicsProcrustes.residuals returns (likewise: the fit keeps its objective's terms to itself)
   FocalSweep  what IntrinsicsSoftmin.residuals returns (likewise: the sweep keeps its error curve and per-candidate poses to itself)
   DepthConsistency  what projection.depth_consistency / Model.consistency return (likewise: the reference never compares its depth maps)
+  RenderedViews  what projection.render_views / Model.render return (likewise: the reference never renders its reconstruction)
 
 The reference's own dataclasses are accepted everywhere these are (duck typing): the
 drop-in never checks the class, only the attribute names.
@@ -20,6 +21,7 @@ from __future__ import annotations
 from dataclasses import dataclass, fields
 from typing import Any, Optional
 
+import torch
 from torch import Tensor
 
 
@@ -190,3 +192,48 @@ class DepthConsistency:
         from .loss.loss import or_one
 
         return self.frame_sum / or_one(self.frame_valid)
+
+
+@dataclass
+class RenderedViews:
+    """The depth maps (and colours) of some source frames splatted into a list of cameras with a z-buffer — projection.render_views /
+    Model.render.  Per target pixel of a view the nearest source pixel that lands in it: p = unproject(xy, depth_i, K_i),
+    q = (E_v⁻¹·E_i)·[p; 1], uv = project_camera_space(q, K_v); the smallest q.z wins, among equal q.z the lower source index."""
+
+    color: Optional[Tensor]  # (batch, V, 3, OH, OW) float32: colors[i, :, y, x] of the winner bit for bit, ``background`` in a hole; None without colors
+    depth: Tensor  # (batch, V, OH, OW) float32: the winner's q.z, 0 in a hole
+    source: Tensor  # (batch, V, OH, OW) int32: the winner's absolute index i·H·W + y·W + x, −1 in a hole
+    source_shape: tuple  # (H, W) of the source frames
+    first_frame: Optional[int] = None  # held-out mode: view v is frame first_frame + v
+    offsets: Optional[tuple] = None  # held-out mode: view v was rendered from the frames first_frame + v + d that exist
+
+    def source_frame(self) -> Tensor:
+        """The source frame of every target pixel (source // (H·W)), −1 in a hole."""
+        h, w = self.source_shape
+        return torch.where(self.source < 0, self.source, torch.div(self.source, h * w, rounding_mode="floor"))
+
+    def coverage(self) -> Tensor:
+        """(batch, V) float64: the share of target pixels that are not holes."""
+        return (self.source >= 0).to(torch.float64).mean(dim=(2, 3))
+
+    def _error_sums(self, images: Tensor, power: int):
+        if self.color is None:
+            raise RuntimeError("flowmap_amd: RenderedViews: there is no colour to compare (render_views(..., colors=...))")
+        if not torch.is_tensor(images) or tuple(images.shape) != tuple(self.color.shape):
+            raise RuntimeError(f"flowmap_amd: RenderedViews: images of shape {tuple(getattr(images, 'shape', ()))}; expected {tuple(self.color.shape)}")
+        covered = (self.source >= 0)[:, :, None]
+        diff = (self.color.to(torch.float64) - images.to(torch.float64)).abs() ** power
+        total = torch.where(covered, diff, torch.zeros_like(diff)).sum(dim=(2, 3, 4))
+        return total, 3.0 * covered.to(torch.float64).sum(dim=(2, 3, 4))
+
+    def abs_error(self, images: Tensor) -> Tensor:
+        """(batch, V) float64: the mean |color − images| over the covered pixels only (NaN for a view without any)."""
+        total, count = self._error_sums(images, 1)
+        return total / count
+
+    def psnr(self, images: Tensor) -> Tensor:
+        """(batch, V) float64: −10·log10 of the mean squared error against ``images`` (batch, V, 3, OH, OW, values in [0, 1]) over the
+        covered pixels only, summed in float64 (NaN for a view without any).  In held-out mode ``psnr(batch.videos[:, window])`` is the
+        held-out score."""
+        total, count = self._error_sums(images, 2)
+        return -10.0 * torch.log10(total / count)

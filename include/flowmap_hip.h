@@ -46,9 +46,10 @@ extern "C" {
  * fm_track_residuals / fm_track_residual_workspace; the existing entries are unchanged; version 11: the alignment residual maps —
  * fm_alignment_residuals / fm_alignment_residual_workspace; the existing entries are unchanged; version 12: the softmin focal sweep per
  * pair — fm_focal_sweep; the existing entries are unchanged; version 13: the depth consistency across frame offsets —
- * fm_depth_consistency / fm_depth_consistency_blocks; the existing entries are unchanged).  A binding checks
+ * fm_depth_consistency / fm_depth_consistency_blocks; the existing entries are unchanged; version 14: the rendered views —
+ * fm_render_views / fm_render_views_workspace; the existing entries are unchanged).  A binding checks
  * fm_abi_version() == FM_ABI_VERSION when it loads the library. */
-#define FM_ABI_VERSION 13
+#define FM_ABI_VERSION 14
 int fm_abi_version(void);
 
 #define FM_STAT_STRIDE 16      /* doubles per pair in `stats` */
@@ -891,6 +892,38 @@ int fm_depth_consistency(const float* depth, const float* k, const float* kinv, 
                          int batch, int frames, int height, int width, int first_frame, int count, float tolerance, float* error,
                          uint8_t* code, float* positions, float* reprojected, float* sampled, uint8_t* support, double* frame_sum,
                          double* frame_valid, float* rel, double* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Rendered views (ABI version 14): z-buffered splats of the depth maps into any camera — a forward warp.  A view v has a camera
+ * (view_k normalised 3x3, view_ext 4x4 camera-to-world) and the (OH, OW) output shape; `pairs` lists which source frames are splatted
+ * into which view.  For a pair (v, i), batch entry b and the pixel of frame i with centre xy (sample_image_grid):
+ *   p = unproject(xy, depth_i, K_i);  q = (E_v⁻¹·E_i)·[p; 1], the relative pose formed in fp64 and rounded once;
+ *   uv = project_camera_space(q, K_v) (its ε = 1e-5 and clamp);  live: q.z > near and 0 <= uv < 1 in both coordinates;
+ *   bin (tx, ty) = (floor(u·OW), floor(v·OH));  with radius r the point covers the (2r+1)² pixels around the bin inside the image;
+ *   every covered pixel receives key = uint64(float_bits(q.z)) << 32 | uint32(i·H·W + y·W + x) and keeps the MINIMUM key: the smallest
+ *   q.z wins, among equal q.z the lower absolute source index (fm_math.h: render_splat_at, render_key).
+ * The result depends on the set of candidates only, never on arrival order: bit-reproducible by construction.
+ *
+ *   depth (B,F,H,W), kinv (B,F,3,3), ext (B,F,4,4) camera-to-world, colors (B,F,3,H,W) or NULL: dense, the whole stacks.
+ *   view_k (B,V,3,3), view_ext (B,V,4,4).  pairs (n_pairs,2) int32, where the other tensors live: (view, source frame); a pair that names
+ *     no view or no frame of this call is skipped.  n_pairs >= 0 (0: every view is all holes), B·n_pairs <= 65535.
+ *   F·H·W < 2^31 (source is int32), H·W and OH·OW < 2^30, B·V·OH·OW <= 2^37, 0 <= radius <= 2, near >= 0 and finite.
+ *   source (B,V,OH,OW) int32 out: the winner's absolute index i·H·W + y·W + x, -1 in a hole.
+ *   out_depth (B,V,OH,OW) out: the winner's q.z, 0 in a hole.
+ *   color (B,V,3,OH,OW) out, given exactly when colors is: colors[i,:,y,x] of the winner bit for bit, `background` in a hole.
+ *   workspace: fm_render_views_workspace bytes, 8-byte aligned, contents unspecified on entry and on return: the (B,V,OH,OW) 64-bit
+ *     z-buffer (8·B·V·OH·OW bytes), then one 16-float pose row per (batch entry, pair) (64·B·n_pairs bytes).
+ * Launches: the z-buffer set to all-ones (a memset on the stream), one thread per (batch entry, pair) for the poses, ONE pass over the
+ * pairs' depth (a thread four adjacent pixels; one 16-byte load when W % 4 == 0 and the base is aligned, else a scalar path with the same
+ * results) with at most one no-return 64-bit atomic minimum per covered target pixel (none where the key already there is smaller), one
+ * resolve thread per target pixel.  EVERY element of
+ * every output is written.
+ *
+ * fm_render_views_workspace: bytes[0] (HOST long) = the workspace size of such a call. */
+int fm_render_views_workspace(int batch, int views, int out_height, int out_width, int n_pairs, long* bytes);
+int fm_render_views(const float* depth, const float* kinv, const float* ext, const float* colors, const float* view_k, const float* view_ext,
+                    const int32_t* pairs, int n_pairs, int batch, int frames, int height, int width, int views, int out_height, int out_width,
+                    int radius, float near, float background, float* color, float* out_depth, int32_t* source, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
