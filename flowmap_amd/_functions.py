@@ -26,6 +26,27 @@ def intrinsics_inverse(k):
 # Function-level building blocks on explicit point sets
 # --------------------------------------------------------------------------------------
 
+MAX_GROUPS = 65535  # groups one call of these entry points takes (they ride on grid.y); more are walked in slices
+
+
+def _group_slices(g: int):
+    """[(first, end)] covering g groups, at most MAX_GROUPS each."""
+    return [(s, min(s + MAX_GROUPS, g)) for s in range(0, g, MAX_GROUPS)]
+
+
+def _rows(t: Optional[Tensor], s: int, e: int) -> Optional[Tensor]:
+    """Groups [s, e) of a contiguous (G, ...) tensor (a view: a whole number of rows, so a pair-aligned tensor stays pair-aligned)."""
+    return t if t is None or (s == 0 and e == t.shape[0]) else t[s:e]
+
+
+def _pairs(t: Tensor, what: str) -> Tensor:
+    """_f32c for a tensor of coordinate pairs, which the kernels move as one float2: a contiguous view that starts an odd number of
+    floats into its allocation is copied to a fresh one (the entry points refuse a pointer that is not 8-byte aligned)."""
+    t = _f32c(t, what)
+    if t.numel() and t.data_ptr() % 8:
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
 
 class Unproject(torch.autograd.Function):
     """unproject (flowmap/model/projection.py:76-90) for G groups of N points:
@@ -34,17 +55,22 @@ class Unproject(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xy, z, k):
         dev = check_device(xy, z, k)
-        xy, z, k = _f32c(xy, "coordinates"), _f32c(z, "z"), _f32c(k, "intrinsics")
         if xy.requires_grad:
             raise RuntimeError("flowmap_amd: gradients w.r.t. image coordinates are not supported")
+        xy, z, k = _pairs(xy, "coordinates"), _f32c(z, "z"), _f32c(k, "intrinsics")
         g, n = z.shape
         shared = xy.dim() == 2
-        kinv = intrinsics_inverse(k)
         out = torch.empty((g, n, 3), dtype=torch.float32, device=dev)
-        with _guard(dev):
-            call("fm_unproject_fwd", ptr(xy), 0 if shared else n * 2, ptr(z), ptr(kinv), g, n, ptr(out), stream_for(z))
-        ctx.save_for_backward(xy, z, kinv)
         ctx.shared = shared
+        if g == 0 or n == 0:  # an empty point set: nothing to launch
+            ctx.save_for_backward(xy, z, torch.empty_like(k))
+            return out
+        kinv = intrinsics_inverse(k)
+        with _guard(dev):
+            for s, e in _group_slices(g):
+                call("fm_unproject_fwd", ptr(xy if shared else _rows(xy, s, e)), 0 if shared else n * 2, ptr(_rows(z, s, e)), ptr(_rows(kinv, s, e)),
+                     e - s, n, ptr(_rows(out, s, e)), stream_for(z))
+        ctx.save_for_backward(xy, z, kinv)
         return out
 
     @staticmethod
@@ -52,13 +78,17 @@ class Unproject(torch.autograd.Function):
         xy, z, kinv = ctx.saved_tensors
         g, n = z.shape
         g_out = _f32c(g_out, "grad")
-        g_z = torch.empty_like(z) if ctx.needs_input_grad[1] else None
         need_k = ctx.needs_input_grad[2]
+        if g == 0 or n == 0:
+            return None, torch.zeros_like(z) if ctx.needs_input_grad[1] else None, torch.zeros_like(kinv) if need_k else None
+        g_z = torch.empty_like(z) if ctx.needs_input_grad[1] else None
         acc = torch.empty((g, 9), dtype=torch.float64, device=z.device) if need_k else None
         g_k = None
         with _guard(z.device):
             st = stream_for(z)
-            call("fm_unproject_bwd", ptr(xy), 0 if ctx.shared else n * 2, ptr(z), ptr(kinv), ptr(g_out), g, n, ptr(g_z), ptr(acc), st)
+            for s, e in _group_slices(g):
+                call("fm_unproject_bwd", ptr(xy if ctx.shared else _rows(xy, s, e)), 0 if ctx.shared else n * 2, ptr(_rows(z, s, e)),
+                     ptr(_rows(kinv, s, e)), ptr(_rows(g_out, s, e)), e - s, n, ptr(_rows(g_z, s, e)), ptr(_rows(acc, s, e)), st)
             if need_k:
                 g_k = torch.empty_like(kinv)
                 call("fm_intrinsics_inverse_bwd", ptr(acc), ptr(kinv), g, ptr(g_k), 0, st)
@@ -76,7 +106,9 @@ class Reproject(torch.autograd.Function):
         g, n, _ = xyz.shape
         out = torch.empty((g, n, 2), dtype=torch.float32, device=dev)
         with _guard(dev):
-            call("fm_reproject_fwd", ptr(xyz), ptr(t), ptr(k), g, n, ptr(out), stream_for(xyz))
+            for s, e in _group_slices(g if n else 0):  # (an empty point set: nothing to launch)
+                call("fm_reproject_fwd", ptr(_rows(xyz, s, e)), ptr(_rows(t, s, e)), ptr(_rows(k, s, e)), e - s, n, ptr(_rows(out, s, e)),
+                     stream_for(xyz))
         ctx.save_for_backward(xyz, t, k)
         return out
 
@@ -84,15 +116,19 @@ class Reproject(torch.autograd.Function):
     def backward(ctx, g_xy):
         xyz, t, k = ctx.saved_tensors
         g, n, _ = xyz.shape
-        g_xy = _f32c(g_xy, "grad")
-        g_xyz = torch.empty_like(xyz) if ctx.needs_input_grad[0] else None
-        g_t = torch.empty_like(t)
-        g_k = torch.empty_like(k)
-        acc = torch.empty((g, 18), dtype=torch.float64, device=xyz.device)
+        g_xy = _pairs(g_xy, "grad")
+        need_xyz, need_t, need_k = ctx.needs_input_grad[:3]
+        if g == 0 or n == 0:
+            return (torch.zeros_like(xyz) if need_xyz else None, torch.zeros_like(t) if need_t else None, torch.zeros_like(k) if need_k else None)
+        g_xyz = torch.empty_like(xyz) if need_xyz else None
+        g_t = torch.empty_like(t) if need_t else None
+        g_k = torch.empty_like(k) if need_k else None
+        acc = torch.empty((min(g, MAX_GROUPS), 18), dtype=torch.float64, device=xyz.device)
         with _guard(xyz.device):
-            call("fm_reproject_bwd", ptr(xyz), ptr(t), ptr(k), ptr(g_xy), g, n, ptr(g_xyz), ptr(g_t), ptr(g_k), ptr(acc),
-                 stream_for(xyz))
-        return g_xyz, g_t if ctx.needs_input_grad[1] else None, g_k if ctx.needs_input_grad[2] else None
+            for s, e in _group_slices(g):
+                call("fm_reproject_bwd", ptr(_rows(xyz, s, e)), ptr(_rows(t, s, e)), ptr(_rows(k, s, e)), ptr(_rows(g_xy, s, e)), e - s, n,
+                     ptr(_rows(g_xyz, s, e)), ptr(_rows(g_t, s, e)), ptr(_rows(g_k, s, e)), ptr(acc), stream_for(xyz))
+        return g_xyz, g_t, g_k
 
 
 class BilinearSample(torch.autograd.Function):
@@ -103,14 +139,15 @@ class BilinearSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, xy):
         dev = check_device(img, xy)
-        img, xy = _f32c(img, "image"), _f32c(xy, "coordinates")
         if xy.requires_grad:
             raise RuntimeError("flowmap_amd: gradients w.r.t. sampling coordinates are not supported")
+        img, xy = _f32c(img, "image"), _pairs(xy, "coordinates")
         g, h, w, c = img.shape
         p = xy.shape[1]
         out = torch.empty((g, p, c), dtype=torch.float32, device=dev)
         with _guard(dev):
-            call("fm_bilinear_sample_fwd", ptr(img), ptr(xy), g, h, w, c, p, ptr(out), stream_for(img))
+            for s, e in _group_slices(g if p and c else 0):  # (an empty point set: nothing to launch)
+                call("fm_bilinear_sample_fwd", ptr(_rows(img, s, e)), ptr(_rows(xy, s, e)), e - s, h, w, c, p, ptr(_rows(out, s, e)), stream_for(img))
         ctx.save_for_backward(xy)
         ctx.dims = (g, h, w, c, p)
         return out
@@ -122,7 +159,8 @@ class BilinearSample(torch.autograd.Function):
         g_out = _f32c(g_out, "grad")
         g_img = torch.zeros((g, h, w, c), dtype=torch.float32, device=xy.device)
         with _guard(xy.device):
-            call("fm_bilinear_sample_bwd", ptr(g_out), ptr(xy), g, h, w, c, p, ptr(g_img), stream_for(xy))
+            for s, e in _group_slices(g if p and g_img.numel() else 0):
+                call("fm_bilinear_sample_bwd", ptr(_rows(g_out, s, e)), ptr(_rows(xy, s, e)), e - s, h, w, c, p, ptr(_rows(g_img, s, e)), stream_for(xy))
         return g_img, None
 
 
@@ -132,11 +170,12 @@ class RobustMapping(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, kind, delta, ax, ay):
         dev = check_device(a, b)
-        a, b = _f32c(a, "a"), _f32c(b, "b")
+        a, b = _pairs(a, "a"), _pairs(b, "b")
         n = a.shape[0]
         out = torch.empty((n,), dtype=torch.float32, device=dev)
-        with _guard(dev):
-            call("fm_mapping_fwd", ptr(a), ptr(b), n, kind, float(delta), float(ax), float(ay), ptr(out), stream_for(a))
+        if n:  # (an empty tensor has no pointer to hand over)
+            with _guard(dev):
+                call("fm_mapping_fwd", ptr(a), ptr(b), n, kind, float(delta), float(ax), float(ay), ptr(out), stream_for(a))
         ctx.save_for_backward(a, b)
         ctx.cfg = (kind, float(delta), float(ax), float(ay))
         return out
@@ -148,8 +187,9 @@ class RobustMapping(torch.autograd.Function):
         g_out = _f32c(g_out, "grad")
         g_a = torch.empty_like(a) if ctx.needs_input_grad[0] else None
         g_b = torch.empty_like(b) if ctx.needs_input_grad[1] else None
-        with _guard(a.device):
-            call("fm_mapping_bwd", ptr(a), ptr(b), ptr(g_out), a.shape[0], kind, delta, ax, ay, ptr(g_a), ptr(g_b), stream_for(a))
+        if a.shape[0]:
+            with _guard(a.device):
+                call("fm_mapping_bwd", ptr(a), ptr(b), ptr(g_out), a.shape[0], kind, delta, ax, ay, ptr(g_a), ptr(g_b), stream_for(a))
         return g_a, g_b, None, None, None, None
 
 
@@ -161,12 +201,16 @@ class AlignRigid(torch.autograd.Function):
         dev = check_device(p, q, w)
         p, q, w = _f32c(p, "p"), _f32c(q, "q"), _f32c(w, "weights")
         g, n, _ = p.shape
+        if g == 0 or n == 0:
+            raise RuntimeError(f"flowmap_amd: align_rigid needs at least one group of at least one point (got {g} groups of {n} points): "
+                               "an empty point set has no rigid fit")
         stats = torch.empty((g, STAT_STRIDE), dtype=torch.float64, device=dev)
         t = torch.empty((g, 4, 4), dtype=torch.float32, device=dev)
         aux = torch.empty((g, AUX_STRIDE), dtype=torch.float64, device=dev)
         with _guard(dev):
             st = stream_for(p)
-            call("fm_align_rigid_stats", ptr(p), ptr(q), ptr(w), g, n, ptr(stats), st)
+            for s, e in _group_slices(g):
+                call("fm_align_rigid_stats", ptr(_rows(p, s, e)), ptr(_rows(q, s, e)), ptr(_rows(w, s, e)), e - s, n, ptr(_rows(stats, s, e)), st)
             call("fm_pose_solve", ptr(stats), g, ptr(t), None, ptr(aux), st)
         ctx.save_for_backward(p, q, w, t, aux)
         return t
@@ -183,5 +227,7 @@ class AlignRigid(torch.autograd.Function):
         with _guard(p.device):
             st = stream_for(p)
             call("fm_pose_solve_bwd", ptr(g_t), None, ptr(t), ptr(aux), g, ptr(pair_grad), None, 0, st)
-            call("fm_align_rigid_bwd", ptr(p), ptr(q), ptr(w), g, n, ptr(aux), ptr(pair_grad), ptr(g_p), ptr(g_q), ptr(g_w), st)
+            for s, e in _group_slices(g):
+                call("fm_align_rigid_bwd", ptr(_rows(p, s, e)), ptr(_rows(q, s, e)), ptr(_rows(w, s, e)), e - s, n, ptr(_rows(aux, s, e)),
+                     ptr(_rows(pair_grad, s, e)), ptr(_rows(g_p, s, e)), ptr(_rows(g_q, s, e)), ptr(_rows(g_w, s, e)), st)
         return g_p, g_q, g_w

@@ -503,6 +503,10 @@ __global__ void random_state_advance_kernel(unsigned long long* state) {
   state[0] = z ^ (z >> 31);
 }
 
+// The kernels read and write coordinate pairs as float2 (unproject's xy, reproject's xy / g_xy, the sampler's xy, the mapping's
+// a / b / g_a / g_b): those pointers must be 8-byte aligned.  Null passes: nullable outputs are checked where they are allowed.
+static inline bool pair_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
 static inline unsigned blocks_for(long n, int per_thread = 4, unsigned cap = 4096) {
   long b = (n + 256L * per_thread - 1) / (256L * per_thread);
   if (b < 1) b = 1;
@@ -515,6 +519,7 @@ extern "C" {
 int fm_unproject_fwd(const float* xy, long xy_group_stride, const float* z, const float* kinv, int groups, long points,
                      float* out, void* stream) {
   FM_CHECK_ARG(xy && z && kinv && out && groups >= 1 && groups <= 65535 && points >= 1);
+  FM_CHECK_ARG(pair_aligned(xy) && (xy_group_stride & 1) == 0);
   hipLaunchKernelGGL(unproject_fwd_kernel, dim3(blocks_for(points), groups), dim3(256), 0, (hipStream_t)stream, xy,
                      xy_group_stride, z, kinv, points, out);
   FM_LAUNCH_STATUS();
@@ -523,6 +528,7 @@ int fm_unproject_fwd(const float* xy, long xy_group_stride, const float* z, cons
 int fm_unproject_bwd(const float* xy, long xy_group_stride, const float* z, const float* kinv, const float* g_out, int groups,
                      long points, float* g_z, double* kinv_acc, void* stream) {
   FM_CHECK_ARG(xy && z && kinv && g_out && groups >= 1 && groups <= 65535 && points >= 1);
+  FM_CHECK_ARG(pair_aligned(xy) && (xy_group_stride & 1) == 0);
   hipStream_t st = (hipStream_t)stream;
   if (kinv_acc && hipMemsetAsync(kinv_acc, 0, sizeof(double) * (size_t)groups * 9, st) != hipSuccess) return FM_ERR_LAUNCH;
   hipLaunchKernelGGL(unproject_bwd_kernel, dim3(blocks_for(points), groups), dim3(256), 0, st, xy, xy_group_stride, z, kinv,
@@ -598,14 +604,14 @@ int fm_random_subset_stateful(unsigned long long* state, long n, long count, int
 }
 
 int fm_reproject_fwd(const float* xyz, const float* t, const float* k, int groups, long points, float* xy, void* stream) {
-  FM_CHECK_ARG(xyz && t && k && xy && groups >= 1 && groups <= 65535 && points >= 1);
+  FM_CHECK_ARG(xyz && t && k && xy && groups >= 1 && groups <= 65535 && points >= 1 && pair_aligned(xy));
   hipLaunchKernelGGL(reproject_fwd_kernel, dim3(blocks_for(points), groups), dim3(256), 0, (hipStream_t)stream, xyz, t, k, points, xy);
   FM_LAUNCH_STATUS();
 }
 
 int fm_reproject_bwd(const float* xyz, const float* t, const float* k, const float* g_xy, int groups, long points, float* g_xyz,
                      float* g_t, float* g_k, double* acc, void* stream) {
-  FM_CHECK_ARG(xyz && t && k && g_xy && acc && groups >= 1 && groups <= 65535 && points >= 1);
+  FM_CHECK_ARG(xyz && t && k && g_xy && acc && groups >= 1 && groups <= 65535 && points >= 1 && pair_aligned(g_xy));
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(acc, 0, sizeof(double) * (size_t)groups * 18, st) != hipSuccess) return FM_ERR_LAUNCH;
   hipLaunchKernelGGL(reproject_bwd_kernel, dim3(blocks_for(points), groups), dim3(256), 0, st, xyz, t, k, g_xy, points, g_xyz, acc);
@@ -615,7 +621,7 @@ int fm_reproject_bwd(const float* xyz, const float* t, const float* k, const flo
 
 int fm_bilinear_sample_fwd(const float* img, const float* xy, int groups, int height, int width, int channels, long points,
                            float* out, void* stream) {
-  FM_CHECK_ARG(img && xy && out && groups >= 1 && groups <= 65535 && points >= 1 && channels >= 1);
+  FM_CHECK_ARG(img && xy && out && groups >= 1 && groups <= 65535 && points >= 1 && channels >= 1 && pair_aligned(xy));
   hipLaunchKernelGGL(bilinear_fwd_kernel, dim3(blocks_for(points, 1), groups), dim3(256), 0, (hipStream_t)stream, img, xy, height,
                      width, channels, points, out);
   FM_LAUNCH_STATUS();
@@ -623,7 +629,7 @@ int fm_bilinear_sample_fwd(const float* img, const float* xy, int groups, int he
 
 int fm_bilinear_sample_bwd(const float* g_out, const float* xy, int groups, int height, int width, int channels, long points,
                            float* g_img, void* stream) {
-  FM_CHECK_ARG(g_out && xy && g_img && groups >= 1 && groups <= 65535 && points >= 1 && channels >= 1);
+  FM_CHECK_ARG(g_out && xy && g_img && groups >= 1 && groups <= 65535 && points >= 1 && channels >= 1 && pair_aligned(xy));
   hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(blocks_for(points, 1), groups), dim3(256), 0, (hipStream_t)stream, g_out, xy, height,
                      width, channels, points, g_img);
   FM_LAUNCH_STATUS();
@@ -631,7 +637,7 @@ int fm_bilinear_sample_bwd(const float* g_out, const float* xy, int groups, int 
 
 int fm_mapping_fwd(const float* a, const float* b, long count, int kind, float delta, float aspect_x, float aspect_y, float* out,
                    void* stream) {
-  FM_CHECK_ARG(a && b && out && count >= 0 && kind >= 0 && kind <= 2);
+  FM_CHECK_ARG(a && b && out && count >= 0 && kind >= 0 && kind <= 2 && pair_aligned(a) && pair_aligned(b));
   if (count == 0) return FM_OK;
   hipLaunchKernelGGL(mapping_fwd_kernel, dim3(blocks_for(count)), dim3(256), 0, (hipStream_t)stream, a, b, count, kind, delta,
                      aspect_x, aspect_y, out);
@@ -641,6 +647,7 @@ int fm_mapping_fwd(const float* a, const float* b, long count, int kind, float d
 int fm_mapping_bwd(const float* a, const float* b, const float* g_out, long count, int kind, float delta, float aspect_x,
                    float aspect_y, float* g_a, float* g_b, void* stream) {
   FM_CHECK_ARG(a && b && g_out && count >= 0 && kind >= 0 && kind <= 2);
+  FM_CHECK_ARG(pair_aligned(a) && pair_aligned(b) && pair_aligned(g_a) && pair_aligned(g_b));
   if (count == 0) return FM_OK;
   hipLaunchKernelGGL(mapping_bwd_kernel, dim3(blocks_for(count)), dim3(256), 0, (hipStream_t)stream, a, b, g_out, count, kind,
                      delta, aspect_x, aspect_y, g_a, g_b);

@@ -330,6 +330,12 @@ int fm_intrinsics_inverse_bwd(const double* kinv_acc, const float* kinv, int cou
  * Function-level building blocks on explicit point sets (the standalone call surface
  * used by the visualiser, IntrinsicsSoftmin and the exporters).  G = number of groups
  * (one small matrix per group), `points` = points per group.
+ *
+ * Limits, checked before anything is launched (else: the argument error).  1 <= G <= 65535 (one launch's grid.y) and
+ * points >= 1 (fm_mapping_*: count >= 0): a caller with more groups walks them in slices, one with none makes no call
+ * (flowmap_amd/_functions.py does both).  Pointers to coordinate PAIRS — fm_unproject_*'s xy (and an even
+ * xy_group_stride), fm_reproject_fwd's xy, fm_reproject_bwd's g_xy, fm_bilinear_sample_*'s xy, fm_mapping_*'s a, b,
+ * g_a, g_b — must be 8-byte aligned: the kernels move a pair as one float2.
  */
 
 /* unproject (projection.py:76-90): out (G,points,3) = (kinv_g·[x,y,1])·z.

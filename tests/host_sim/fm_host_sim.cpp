@@ -1058,8 +1058,12 @@ int fm_intrinsics_inverse_bwd(const double* kinv_acc, const float* kinv, int cou
 }
 
 
+// The library's alignment check of the pointers its kernels read or write as float2 (fm_points.hip: pair_aligned).
+static inline bool pair_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
 int fm_unproject_fwd(const float* xy, long xy_group_stride, const float* z, const float* kinv, int groups, long points,
                      float* out, void*) {
+  if (!pair_aligned(xy) || (xy_group_stride & 1) != 0) return 1;
   for (int g = 0; g < groups; ++g) {
     Mat3 ki;
     load_mat3(kinv + (size_t)g * 9, ki);
@@ -1076,6 +1080,7 @@ int fm_unproject_fwd(const float* xy, long xy_group_stride, const float* z, cons
 
 int fm_unproject_bwd(const float* xy, long xy_group_stride, const float* z, const float* kinv, const float* g_out, int groups,
                      long points, float* g_z, double* kinv_acc, void*) {
+  if (!pair_aligned(xy) || (xy_group_stride & 1) != 0) return 1;
   if (kinv_acc) std::memset(kinv_acc, 0, sizeof(double) * (size_t)groups * 9);
   for (int g = 0; g < groups; ++g) {
     Mat3 ki;
@@ -1097,6 +1102,7 @@ int fm_unproject_bwd(const float* xy, long xy_group_stride, const float* z, cons
 }
 
 int fm_reproject_fwd(const float* xyz, const float* t, const float* k, int groups, long points, float* xy, void*) {
+  if (!pair_aligned(xy)) return 1;
   for (int g = 0; g < groups; ++g) {
     Pose tr;
     Mat3 kk;
@@ -1116,6 +1122,7 @@ int fm_reproject_fwd(const float* xyz, const float* t, const float* k, int group
 
 int fm_reproject_bwd(const float* xyz, const float* t, const float* k, const float* g_xy, int groups, long points, float* g_xyz,
                      float* g_t, float* g_k, double* acc, void*) {
+  if (!pair_aligned(g_xy)) return 1;
   std::memset(acc, 0, sizeof(double) * (size_t)groups * 18);
   for (int g = 0; g < groups; ++g) {
     Pose tr;
@@ -1160,6 +1167,7 @@ int fm_reproject_bwd(const float* xyz, const float* t, const float* k, const flo
 }
 
 int fm_bilinear_sample_fwd(const float* img, const float* xy, int groups, int h, int w, int c, long points, float* out, void*) {
+  if (!pair_aligned(xy)) return 1;
   for (int g = 0; g < groups; ++g) {
     const float* im = img + (size_t)g * h * w * c;
     for (long i = 0; i < points; ++i) {
@@ -1177,6 +1185,7 @@ int fm_bilinear_sample_fwd(const float* img, const float* xy, int groups, int h,
 }
 
 int fm_bilinear_sample_bwd(const float* g_out, const float* xy, int groups, int h, int w, int c, long points, float* g_img, void*) {
+  if (!pair_aligned(xy)) return 1;
   for (int g = 0; g < groups; ++g) {
     float* gi = g_img + (size_t)g * h * w * c;
     for (long i = 0; i < points; ++i) {
@@ -1191,6 +1200,7 @@ int fm_bilinear_sample_bwd(const float* g_out, const float* xy, int groups, int 
 }
 
 int fm_mapping_fwd(const float* a, const float* b, long count, int kind, float delta, float ax, float ay, float* out, void*) {
+  if (!pair_aligned(a) || !pair_aligned(b)) return 1;
   for (long i = 0; i < count; ++i) {
     float dx, dy;
     out[i] = robust_map(kind, delta, aspect_diff(a[2 * i], b[2 * i], ax), aspect_diff(a[2 * i + 1], b[2 * i + 1], ay), dx, dy);
@@ -1200,6 +1210,7 @@ int fm_mapping_fwd(const float* a, const float* b, long count, int kind, float d
 
 int fm_mapping_bwd(const float* a, const float* b, const float* g_out, long count, int kind, float delta, float ax, float ay,
                    float* g_a, float* g_b, void*) {
+  if (!pair_aligned(a) || !pair_aligned(b) || !pair_aligned(g_a) || !pair_aligned(g_b)) return 1;
   for (long i = 0; i < count; ++i) {
     float dx, dy;
     robust_map(kind, delta, aspect_diff(a[2 * i], b[2 * i], ax), aspect_diff(a[2 * i + 1], b[2 * i + 1], ay), dx, dy);
