@@ -127,6 +127,8 @@ SIGNATURES = {
     "fm_depth_consistency": [P] * 5 + [I] * 7 + [F] + [P] * 11,
     "fm_render_views_workspace": [I, I, I, I, I, P],
     "fm_render_views": [P] * 7 + [I] * 9 + [F, F] + [P] * 5,
+    "fm_voxel_cloud_workspace": [L, P, P],
+    "fm_voxel_cloud": [P] * 5 + [I, I, I, D, I, L] + [P] * 9,
 }
 
 _lib: Optional[ctypes.CDLL] = None

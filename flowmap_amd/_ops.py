@@ -242,7 +242,7 @@ def _dense_flow_is_rough(bwd_flow: Tensor, h: int, w: int) -> bool:
 # which backward path the facades selected (tests)
 counters = {"procrustes_planned": 0, "procrustes_dense_planned": 0, "flow_packs": 0, "flow_packs_bitmask": 0, "procrustes_plans_built": 0, "track_tap_samples": 0,
             "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0, "flow_residuals": 0, "track_residuals": 0, "alignment_residuals": 0, "focal_sweep": 0,
-            "depth_consistency": 0, "render_views": 0}
+            "depth_consistency": 0, "render_views": 0, "voxel_cloud": 0}
 
 
 class LeadingFrames:
@@ -887,6 +887,18 @@ def render_views(depth, kinv, ext, colors, view_k, view_ext, pairs, shape, radiu
                                                         float(near), float(background))
     counters["render_views"] += 1
     return (color if colors is not None else None), out_depth, source
+
+
+def voxel_cloud(depth, kinv, ext, colors, keep, voxel_size, min_count, capacity, details):
+    """The world points of ``depth`` (F,H,W) merged per cell of a grid of edge ``voxel_size`` (csrc/fm_torch.cpp: voxel_cloud_op ->
+    fm_voxel_cloud): (xyz, rgb, count, first, slot, pixel_slot, counters) — ``capacity`` rows each, written up to counters[0] and in no
+    particular order; rgb None without ``colors``, pixel_slot None without ``details``; counters: 8 int64 on the device (rows drawn,
+    points without a slot, masked, invalid, out of range).  Three memsets, one pass over depth with 64-bit integer atomics, one pass
+    over the table.  Reads its arguments and nothing else."""
+    xyz, rgb, count, first, slot, pixel_slot, counts = torch_ops().voxel_cloud(depth, kinv, ext, colors, keep, float(voxel_size), int(min_count), int(capacity),
+                                                                               bool(details))
+    counters["voxel_cloud"] += 1
+    return xyz, (rgb if colors is not None else None), count, first, slot, (pixel_slot if details else None), counts
 
 
 def softmin_intrinsics(depth, weights, bwd_flow, indices, candidate_k, rel, weight_sens, frames):

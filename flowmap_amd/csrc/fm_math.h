@@ -132,6 +132,39 @@ FM_HD void apply_pose(const Pose& t, const float x[3], float o[3]) {
   o[2] = t.r[6] * x[0] + t.r[7] * x[1] + t.r[8] * x[2] + t.t[2];
 }
 
+#if defined(__clang__)
+#define FM_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define FM_NO_CONTRACT
+#endif
+
+// The world point of one pixel (export.world_point_cloud, export.voxel_point_cloud; fm_points.hip: world_points_kernel and
+// fm_voxel_cloud.hip: voxel_insert_kernel both call this): ray = K⁻¹[u,v,1], p = ray·z, out = (E·[p;1])[:3].
+// Two kernels must agree on it TO THE BIT — the voxel of a point is a floor of it —, so on the device the roundings are written
+// out instead of left to the compiler's contraction, which follows the code around a statement: the fused multiply-adds below are
+// exactly the ones world_points_kernel has always been compiled to for gfx950 (its output is unchanged), now in every context.
+// A host compiler evaluates the plain form, product by product, as the serial build of fm_world_points does.
+FM_HD void world_point_at(const Mat3& kinv, const Pose& e, float u, float v, float z, float out[3]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  FM_NO_CONTRACT
+  const float* m = kinv.m;
+  const float r0 = __builtin_fmaf(m[1], v, m[0] * u) + m[2];
+  const float r1 = __builtin_fmaf(m[3], u, m[4] * v) + m[5];
+  const float r2 = (m[6] * u + m[7] * v) + m[8];
+  const float x = r0 * z, y = r1 * z, w = r2 * z;
+  out[0] = __builtin_fmaf(e.r[2], w, __builtin_fmaf(e.r[1], y, e.r[0] * x)) + e.t[0];
+  out[1] = __builtin_fmaf(e.r[5], w, __builtin_fmaf(e.r[3], x, e.r[4] * y)) + e.t[1];
+  out[2] = __builtin_fmaf(e.r[8], w, __builtin_fmaf(e.r[6], x, e.r[7] * y)) + e.t[2];
+#else
+  float ray[3], p[3];
+  ray_dir(kinv, u, v, ray);
+  p[0] = ray[0] * z;
+  p[1] = ray[1] * z;
+  p[2] = ray[2] * z;
+  apply_pose(e, p, out);
+#endif
+}
+
 FM_HD void apply_rot_t(const Pose& t, const float g[3], float o[3]) {  // Rᵀ g
   o[0] = t.r[0] * g[0] + t.r[3] * g[1] + t.r[6] * g[2];
   o[1] = t.r[1] * g[0] + t.r[4] * g[1] + t.r[7] * g[2];
@@ -595,6 +628,100 @@ FM_HD void render_footprint(const RenderSplat& s, int radius, int oh, int ow, Fn
       fn((size_t)y * ow + x);
     }
   }
+}
+
+// ---------------------------------------------------------------------------------
+// The voxel of ONE world point and what it adds to it (export.voxel_point_cloud; fm_voxel_cloud.hip and its host twin both call
+// these).  Everything a point contributes is an INTEGER, so a voxel's record is a function of the set of its points:
+//   per axis  t = x·inv (one fp32 multiply, inv = (float)(1/voxel_size)),  cell = floorf(t),  frac = t − cell,
+//             q = min((uint32)(frac·2²⁰), 2²⁰ − 1)   (frac is exact and < 1 but for a tiny negative t, where t + 1 rounds to 1: the min);
+//             the point is out of range unless −2²⁰ <= cell < 2²⁰ on all three axes;
+//   key       the three cells, biased by 2²⁰, packed 21 bits each (x highest): 63 bits, all-ones is "empty";
+//   colour    (uint32)(clamp(c, 0, 1)·2¹⁶) per channel, a NaN counting as 0;
+//   finalize  xyz = (cell + (sum/count + 0.5)/2²⁰)·voxel_size,  rgb = sum/count/2¹⁶, in fp64, rounded once to fp32.
+// A record: [0..2] Σq per axis, [3..5] Σ colour, [6] count, [7] the maximum of ~index (all-ones minus the linear index: the
+// minimum index as a maximum, so that a zeroed record is an empty one).
+// ---------------------------------------------------------------------------------
+constexpr unsigned long long kVoxelEmpty = ~0ULL;
+constexpr int kVoxelCellBits = 21;
+constexpr float kVoxelCellLimit = 1048576.f;  // 2²⁰: cells lie in [−2²⁰, 2²⁰)
+constexpr int kVoxelRecord = 8;               // 8-byte words per record: 64 bytes
+enum VoxelClass : int { kVoxelLive = 0, kVoxelMasked = 1, kVoxelInvalid = 2, kVoxelOutOfRange = 3 };
+
+FM_HD bool voxel_axis(float x, float inv, unsigned int& biased, unsigned int& q) {
+  FM_NO_CONTRACT
+  const float t = x * inv;
+  const float cell = floorf(t);
+  if (!(cell >= -kVoxelCellLimit && cell < kVoxelCellLimit)) return false;
+  const float frac = t - cell;
+  const unsigned int scaled = (unsigned int)(frac * 1048576.f);
+  q = scaled < 1048575u ? scaled : 1048575u;
+  biased = (unsigned int)((int)cell + 1048576);
+  return true;
+}
+
+FM_HD unsigned long long voxel_key(unsigned int bx, unsigned int by, unsigned int bz) {
+  return ((unsigned long long)bx << (2 * kVoxelCellBits)) | ((unsigned long long)by << kVoxelCellBits) | (unsigned long long)bz;
+}
+
+FM_HD unsigned long long voxel_hash(unsigned long long key) {  // (the 64-bit finalizer of MurmurHash3)
+  key ^= key >> 33;
+  key *= 0xff51afd7ed558ccdULL;
+  key ^= key >> 33;
+  key *= 0xc4ceb9fe1a85ec53ULL;
+  key ^= key >> 33;
+  return key;
+}
+
+FM_HD unsigned int voxel_color(float c) {
+  FM_NO_CONTRACT
+  const float clamped = c > 0.f ? (c < 1.f ? c : 1.f) : 0.f;
+  return (unsigned int)(clamped * 65536.f);
+}
+
+struct VoxelPoint {
+  unsigned long long key;
+  unsigned int q[3];
+  int cls;  // VoxelClass
+};
+
+// `kept`: the caller's mask; z: the pixel's depth; xw: world_point_at of it.
+FM_HD VoxelPoint voxel_point(bool kept, float z, const float xw[3], float inv) {
+  VoxelPoint o;
+  o.key = kVoxelEmpty;
+  o.q[0] = o.q[1] = o.q[2] = 0u;
+  const float inf = __builtin_inff();
+  if (!kept) {
+    o.cls = kVoxelMasked;
+    return o;
+  }
+  const bool finite = xw[0] > -inf && xw[0] < inf && xw[1] > -inf && xw[1] < inf && xw[2] > -inf && xw[2] < inf;
+  if (!(z > 0.f && z < inf) || !finite) {
+    o.cls = kVoxelInvalid;
+    return o;
+  }
+  unsigned int b[3];
+  if (!(voxel_axis(xw[0], inv, b[0], o.q[0]) && voxel_axis(xw[1], inv, b[1], o.q[1]) && voxel_axis(xw[2], inv, b[2], o.q[2]))) {
+    o.q[0] = o.q[1] = o.q[2] = 0u;
+    o.cls = kVoxelOutOfRange;
+    return o;
+  }
+  o.key = voxel_key(b[0], b[1], b[2]);
+  o.cls = kVoxelLive;
+  return o;
+}
+
+// One finished voxel from its key and record (count >= 1): xyz[3], rgb[3] (rgb may be null), -> the lowest linear index.
+FM_HD long long voxel_finalize(unsigned long long key, const unsigned long long* rec, double voxel_size, float* xyz, float* rgb) {
+  FM_NO_CONTRACT
+  const double count = (double)rec[6];
+  for (int a = 0; a < 3; ++a) {
+    const int cell = (int)((key >> ((2 - a) * kVoxelCellBits)) & 0x1fffffULL) - 1048576;
+    const double mean = (double)rec[a] / count;
+    xyz[a] = (float)(((double)cell + (mean + 0.5) / 1048576.0) * voxel_size);
+    if (rgb) rgb[a] = (float)((double)rec[3 + a] / count / 65536.0);
+  }
+  return (long long)~rec[7];
 }
 
 // ---------------------------------------------------------------------------------
@@ -1415,4 +1542,5 @@ FM_HD void dense_bwd_s(const DenseBwd& c, const float h[3], const float t[3], co
 #include "fm_focal_sweep_host.h"
 #include "fm_depth_consistency_host.h"
 #include "fm_render_views_host.h"
+#include "fm_voxel_cloud_host.h"
 #endif

@@ -299,11 +299,8 @@ __global__ void __launch_bounds__(256) world_points_kernel(const float* depth, c
   load_pose44(ext + (size_t)fr * 16, e);
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const int row = (int)(i / w), col = (int)(i - (size_t)row * w);
-    float ray[3], xyz[3], xw[3];
-    ray_dir(ki, pixel_center(col, w), pixel_center(row, h), ray);
-    const float z = depth[(size_t)fr * n + i];
-    xyz[0] = ray[0] * z; xyz[1] = ray[1] * z; xyz[2] = ray[2] * z;
-    apply_pose(e, xyz, xw);
+    float xw[3];
+    world_point_at(ki, e, pixel_center(col, w), pixel_center(row, h), depth[(size_t)fr * n + i], xw);
     float* o = out_xyz + ((size_t)fr * n + i) * 3;
     o[0] = xw[0]; o[1] = xw[1]; o[2] = xw[2];
     if (colors) {

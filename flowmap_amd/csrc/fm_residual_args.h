@@ -1,5 +1,5 @@
 // Argument checks and size formulas of the residual entry points (include/flowmap_hip.h: fm_flow_residuals, fm_track_residuals,
-// fm_alignment_residuals, fm_focal_sweep, fm_depth_consistency, fm_render_views and their size functions), stated ONCE: the device build (fm_*.hip) and the serial host build of
+// fm_alignment_residuals, fm_focal_sweep, fm_depth_consistency, fm_render_views, fm_voxel_cloud and their size functions), stated ONCE: the device build (fm_*.hip) and the serial host build of
 // the same ABI (fm_*_host.h) both call these, so the two refuse the same calls and size the same workspaces.  Plain C++, no HIP.
 // Device-only, and therefore not here: the 16-byte path's eligibility and the pointer alignment the kernels need (the host build reads
 // element by element and never touches the workspace).
@@ -162,6 +162,35 @@ static inline bool render_views_args_ok(const float* depth, const float* kinv, c
   if (!(frames >= 1 && res_frame_ok(height, width) && (long)frames * height * width < kRenderMaxSources)) return false;
   if (radius < 0 || radius > kRenderMaxRadius) return false;
   return near >= 0.f && near < __builtin_inff() && background == background;
+}
+
+// ---- voxel point cloud ----
+constexpr int kVoxelTile = 1024;              // pixels per workgroup of voxel_insert_kernel (the geometry of render_splat_kernel)
+constexpr long kVoxelMaxCapacity = 1L << 28;  // rows of one call: the table has at most 2^30 slots, a slot index is an int32
+constexpr int kVoxelCounters = 8;             // 8-byte words of `counters`: rows drawn, overflow, masked, invalid, out of range, 3 spare
+// the table: the smallest power of two >= 2·capacity slots (load factor <= 1/2), a 64-byte record and an 8-byte key per slot
+static inline long voxel_cloud_slots(long capacity) {
+  long slots = 2;
+  while (slots < 2 * capacity) slots *= 2;
+  return slots;
+}
+static inline long voxel_cloud_workspace_bytes(long capacity) { return 72 * voxel_cloud_slots(capacity); }
+static inline bool voxel_cloud_workspace_args_ok(long capacity, const long* slots, const long* bytes) {
+  return slots && bytes && capacity >= 1 && capacity <= kVoxelMaxCapacity;
+}
+static inline bool voxel_cloud_args_ok(const float* depth, const float* kinv, const float* ext, const float* colors, const uint8_t* keep, int frames,
+                                       int height, int width, double voxel_size, int min_count, long capacity, const float* xyz, const float* rgb,
+                                       const int32_t* count, const int64_t* first, const int32_t* slot, const int32_t* pixel_slot,
+                                       const unsigned long long* counters, const void* workspace) {
+  (void)keep, (void)pixel_slot;  // (optional)
+  if (!(depth && kinv && ext && xyz && count && first && slot && counters && workspace)) return false;
+  if ((colors != nullptr) != (rgb != nullptr)) return false;
+  if (!(frames >= 1 && frames <= kResMaxRows && res_frame_ok(height, width) && (long)frames * height * width < kRenderMaxSources)) return false;
+  const float inv = (float)(1.0 / voxel_size);  // (finite and normal, or the call is refused)
+  if (!(voxel_size > 0.0 && voxel_size < (double)__builtin_inff() && inv >= 1.17549435e-38f && inv < __builtin_inff())) return false;
+  if (min_count < 1 || capacity < 1 || capacity > kVoxelMaxCapacity) return false;
+  // the records are 64-byte requests, the counters 8-byte words: both builds refuse a misaligned pointer
+  return (reinterpret_cast<uintptr_t>(workspace) & 63) == 0 && (reinterpret_cast<uintptr_t>(counters) & 7) == 0;
 }
 
 }  // namespace fm

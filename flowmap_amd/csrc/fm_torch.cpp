@@ -51,7 +51,8 @@ using OptTensor = std::optional<Tensor>;
   X(fm_adam_step_capturable) X(fm_softmin_score_fwd) X(fm_softmin_score_bwd) X(fm_softmin_blend_fwd) X(fm_softmin_blend_bwd)         \
   X(fm_random_subset) X(fm_random_subset_stateful) X(fm_abi_version) X(fm_flow_loss_fused_taps) X(fm_track_loss_fused_fwd_taps) X(fm_tap_grad_apply) \
   X(fm_flow_loss_fused_bitmask) X(fm_flow_residuals) X(fm_flow_residual_blocks) X(fm_track_residuals) X(fm_track_residual_workspace) \
-  X(fm_depth_consistency) X(fm_depth_consistency_blocks) X(fm_render_views) X(fm_render_views_workspace)
+  X(fm_depth_consistency) X(fm_depth_consistency_blocks) X(fm_render_views) X(fm_render_views_workspace) \
+  X(fm_voxel_cloud) X(fm_voxel_cloud_workspace)
 
 struct Api {
 #define X(name) decltype(&::name) name = nullptr;
@@ -1722,6 +1723,42 @@ static std::vector<Tensor> render_views_op(const Tensor& depth_in, const Tensor&
   return {color, out_depth, source};
 }
 
+// export.voxel_point_cloud (fm_voxel_cloud): the world points of the depth maps merged per cell of a world-space grid in one pass over
+// depth.  Not differentiable.  -> {xyz, rgb (empty without colors), count, first, slot: `capacity` rows each, written up to the rows
+// drawn and in no particular order; pixel_slot (F,H,W; empty without details); counters (8 int64 on the device)}.  The hash table is
+// this call's only scratch.
+static std::vector<Tensor> voxel_cloud_op(const Tensor& depth_in, const Tensor& kinv_in, const Tensor& ext_in, const OptTensor& colors_in, const OptTensor& keep_in,
+                                          double voxel_size, int64_t min_count, int64_t capacity, bool details) {
+  at::NoGradGuard no_grad;
+  const bool has_colors = colors_in.has_value() && colors_in->defined(), has_keep = keep_in.has_value() && keep_in->defined();
+  const Tensor colors_t = has_colors ? *colors_in : Tensor(), keep_t = has_keep ? *keep_in : Tensor();
+  const auto dev = check_device({&depth_in, &kinv_in, &ext_in, &colors_t, &keep_t});
+  const Tensor depth = f32c(depth_in.detach(), "depths"), kinv = f32c(kinv_in.detach(), "inverse intrinsics"), ext = f32c(ext_in.detach(), "extrinsics");
+  const Tensor colors = has_colors ? f32c(colors_t.detach(), "colors") : Tensor();
+  TORCH_CHECK(depth.dim() == 3, "flowmap_amd: depths must be (frame, height, width)");
+  const int64_t f = depth.size(0), h = depth.size(1), w = depth.size(2);
+  TORCH_CHECK(f >= 1 && f <= 65535 && h * w >= 1 && h * w < (int64_t(1) << 30) && f * h * w < (int64_t(1) << 31),
+              "flowmap_amd: voxel_point_cloud indexes pixels with int32 and takes at most 65 535 frames per call (got ", f, " x ", h, " x ", w, ")");
+  TORCH_CHECK(kinv.sizes() == at::IntArrayRef({f, 3, 3}) && ext.sizes() == at::IntArrayRef({f, 4, 4}), "flowmap_amd: intrinsics / extrinsics do not match the depths");
+  TORCH_CHECK(!has_colors || colors.sizes() == at::IntArrayRef({f, 3, h, w}), "flowmap_amd: colors must be (frame, 3, height, width)");
+  TORCH_CHECK(!has_keep || (keep_t.scalar_type() == at::kBool && keep_t.sizes() == depth.sizes()), "flowmap_amd: keep must be a bool tensor shaped like the depths");
+  const Tensor keep = has_keep ? keep_t.contiguous() : Tensor();
+  TORCH_CHECK(capacity >= 1 && capacity <= (int64_t(1) << 28), "flowmap_amd: voxel_point_cloud: capacity must be in [1, 2^28] (got ", capacity, ")");
+  long slots = 0, bytes = 0;
+  FM_CALL(fm_voxel_cloud_workspace, (long)capacity, &slots, &bytes);
+  const auto fopt = depth.options();
+  Tensor work = at::empty({((int64_t)bytes + 7) / 8}, fopt.dtype(at::kLong));
+  Tensor xyz = at::empty({capacity, 3}, fopt), rgb = has_colors ? at::empty({capacity, 3}, fopt) : at::empty({0}, fopt);
+  Tensor count = at::empty({capacity}, fopt.dtype(at::kInt)), first = at::empty({capacity}, fopt.dtype(at::kLong)), slot = at::empty({capacity}, fopt.dtype(at::kInt));
+  Tensor pixel_slot = details ? at::empty({f, h, w}, fopt.dtype(at::kInt)) : at::empty({0}, fopt.dtype(at::kInt));
+  Tensor counters = at::empty({8}, fopt.dtype(at::kLong));
+  DeviceScope scope(dev);
+  FM_CALL(fm_voxel_cloud, ptr(depth), ptr(kinv), ptr(ext), has_colors ? ptr(colors) : nullptr, has_keep ? ptr<uint8_t>(keep) : nullptr, (int)f, (int)h, (int)w,
+          voxel_size, (int)min_count, (long)capacity, ptr(xyz), has_colors ? ptr(rgb) : nullptr, ptr<int32_t>(count), ptr<int64_t>(first), ptr<int32_t>(slot),
+          details ? ptr<int32_t>(pixel_slot) : nullptr, ptr<unsigned long long>(counters), work.data_ptr(), scope.stream);
+  return {xyz, rgb, count, first, slot, pixel_slot, counters};
+}
+
 }  // namespace fmt
 
 TORCH_LIBRARY(flowmap_amd, m) {
@@ -1809,4 +1846,6 @@ TORCH_LIBRARY(flowmap_amd, m) {
   m.def("render_views(Tensor depth, Tensor kinv, Tensor ext, Tensor? colors, Tensor view_k, Tensor view_ext, Tensor pairs, int out_h, int out_w, int radius, "
         "float near, float background) -> Tensor[]",
         fmt::render_views_op);
+  m.def("voxel_cloud(Tensor depth, Tensor kinv, Tensor ext, Tensor? colors, Tensor? keep, float voxel_size, int min_count, int capacity, bool details) -> Tensor[]",
+        fmt::voxel_cloud_op);
 }

@@ -3,6 +3,8 @@
 * ``world_point_cloud``: the point cloud ``export_to_colmap`` builds frame by frame
   (flowmap/export/colmap.py:86-101: unproject, homogenise, camera-to-world, colours to
   point-major), as ONE launch (fm_world_points) instead of F × (unproject + einsum + 2 copies).
+* ``voxel_point_cloud``: the same points merged per cell of a world-space grid — one averaged point and colour per occupied voxel, a
+  count and the lowest contributing pixel —, in ONE pass over depth (fm_voxel_cloud) with no point cloud formed; bit-reproducible.
 * ``write_ply``: the vertex layout of colmap.py:31-53 (x y z nx ny nz red green blue, binary
   little-endian — what 3D Gaussian Splatting reads), written with numpy alone.
 * ``compute_ate``: flowmap/misc/ate.py:7-25 (scipy Procrustes alignment, RMS over all
@@ -22,15 +24,13 @@ from torch import Tensor
 
 from . import _ops
 from ._lib import call, check_device, ptr, stream_for
+from .types import VoxelCloud
+
+VOXEL_MAX_CAPACITY = 1 << 28  # (fm_residual_args.h: kVoxelMaxCapacity)
 
 
-def world_point_cloud(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, colors: Optional[Tensor] = None,
-                      keep: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
-    """depths (F,H,W), intrinsics (F,3,3), extrinsics (F,4,4) camera-to-world, colors
-    (F,3,H,W) -> world points (F·H·W,3) and colours (F·H·W,3), frames concatenated in order
-    (colmap.py:86-101 with ``exports.*[0]``).  ``keep``: a bool (F,H,W) mask on the depths' device — the points and colours
-    returned are the kept ones, in the same order (e.g. ``depth_consistency(...).support[0] >= 2``: the points that at least two
-    other frames confirm); None: every point."""
+def _check_cloud_arguments(depths, intrinsics, extrinsics, colors, keep) -> Tuple[int, int, int]:
+    """The checks world_point_cloud and voxel_point_cloud share -> (frames, height, width)."""
     check_device(depths, intrinsics, extrinsics, *(() if colors is None else (colors,)))
     if depths.dim() != 3:
         raise RuntimeError("flowmap_amd: depths must be (frame, height, width)")
@@ -46,6 +46,17 @@ def world_point_cloud(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, co
             raise RuntimeError(f"flowmap_amd: keep of shape {tuple(keep.shape)} does not match the depths {(f, h, w)}")
         if keep.device != depths.device:
             raise RuntimeError(f"flowmap_amd: keep is on {keep.device}, the depths on {depths.device}")
+    return f, h, w
+
+
+def world_point_cloud(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, colors: Optional[Tensor] = None,
+                      keep: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
+    """depths (F,H,W), intrinsics (F,3,3), extrinsics (F,4,4) camera-to-world, colors
+    (F,3,H,W) -> world points (F·H·W,3) and colours (F·H·W,3), frames concatenated in order
+    (colmap.py:86-101 with ``exports.*[0]``).  ``keep``: a bool (F,H,W) mask on the depths' device — the points and colours
+    returned are the kept ones, in the same order (e.g. ``depth_consistency(...).support[0] >= 2``: the points that at least two
+    other frames confirm); None: every point."""
+    f, h, w = _check_cloud_arguments(depths, intrinsics, extrinsics, colors, keep)
     with torch.no_grad():
         depths, extrinsics = _ops._f32c(depths, "depths"), _ops._f32c(extrinsics, "extrinsics")
         kinv = _ops.intrinsics_inverse(_ops._f32c(intrinsics, "intrinsics"))
@@ -58,6 +69,68 @@ def world_point_cloud(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, co
             kept = keep.reshape(-1)
             xyz, rgb = xyz[kept], None if rgb is None else rgb[kept]
     return xyz, rgb
+
+
+VOXEL_DEFAULT_DIVISOR = 16  # default capacity: one voxel per 16 candidate pixels (at least VOXEL_DEFAULT_FLOOR, at most the candidates)
+VOXEL_DEFAULT_FLOOR = 4096
+
+
+def voxel_default_capacity(candidates: int) -> int:
+    """The ``capacity`` voxel_point_cloud takes when none is given: the candidate pixels, capped at max(candidates // 16, 4096).  The
+    table has fewer than 4·capacity slots of 72 bytes, so beyond 65 536 candidates the workspace stays below 18 bytes per candidate
+    pixel: 4.5 times the depth tensor."""
+    return max(1, min(candidates, max(candidates // VOXEL_DEFAULT_DIVISOR, VOXEL_DEFAULT_FLOOR)))
+
+
+def voxel_point_cloud(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, colors: Optional[Tensor], voxel_size: float, *,
+                      keep: Optional[Tensor] = None, min_count: int = 1, capacity: Optional[int] = None, details: bool = False) -> VoxelCloud:
+    """The points of ``world_point_cloud`` (same arguments, same checks) merged per cell of a world-space grid of edge ``voxel_size``:
+    one centroid, mean colour, point count and lowest linear index ``frame·H·W + pixel`` per occupied voxel, rows in ascending lowest
+    index -> VoxelCloud.  One pass over depth (fm_voxel_cloud: a hash table of integer accumulators; no point cloud is formed), so the
+    result is a function of the SET of points: bit-reproducible.
+
+    ``keep``: a bool (F,H,W) mask — only these pixels take part (``depth_consistency(...).support[0] >= 2``).  ``min_count``: a voxel
+    with fewer points is left out (it is not an error and not counted in ``dropped``).  ``capacity``: the most voxels the call can
+    hold — the table and the outputs are sized by it; None: ``voxel_default_capacity`` of the candidate pixels (F·H·W, or ``keep``'s
+    count).  A cloud that does not fit raises and names ``capacity``.  ``details``: also ``voxel_of`` (F,H,W), the row of each pixel.
+    A point is dropped as ``masked`` (keep), ``invalid`` (depth not finite or <= 0, or a non-finite world coordinate) or
+    ``out_of_range`` (a cell outside [−2²⁰, 2²⁰) — a larger ``voxel_size`` brings it in)."""
+    f, h, w = _check_cloud_arguments(depths, intrinsics, extrinsics, colors, keep)
+    if isinstance(voxel_size, bool) or not isinstance(voxel_size, (int, float)) or not (0.0 < float(voxel_size) < float("inf")):
+        raise ValueError(f"flowmap_amd: voxel_point_cloud: voxel_size must be a finite number > 0 (got {voxel_size!r})")
+    with np.errstate(over="ignore"):
+        inverse = np.float32(1.0 / float(voxel_size))
+    if not (2.0**-126 <= float(inverse) < float("inf")):
+        raise ValueError(f"flowmap_amd: voxel_point_cloud: voxel_size = {voxel_size!r} has no finite, normal float32 reciprocal")
+    if isinstance(min_count, bool) or not isinstance(min_count, int) or min_count < 1:
+        raise ValueError(f"flowmap_amd: voxel_point_cloud: min_count must be an integer >= 1 (got {min_count!r})")
+    if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, int) or not 1 <= capacity <= VOXEL_MAX_CAPACITY):
+        raise ValueError(f"flowmap_amd: voxel_point_cloud: capacity must be an integer in [1, 2^28] (got {capacity!r})")
+    if not isinstance(details, bool):
+        raise ValueError(f"flowmap_amd: voxel_point_cloud: details must be a bool (got {details!r})")
+    if f > 65535 or h * w >= 1 << 30 or f * h * w >= 1 << 31:
+        raise ValueError(f"flowmap_amd: voxel_point_cloud: frames x height x width = {f} x {h} x {w} does not fit (at most 65535 frames, int32 pixel indices)")
+    with torch.no_grad():
+        if capacity is None:  # (counting a mask's candidates waits for the device once more: pass capacity to avoid it)
+            capacity = min(voxel_default_capacity(f * h * w if keep is None else int(keep.sum())), VOXEL_MAX_CAPACITY)
+        kinv = _ops.intrinsics_inverse_peek(_ops._f32c(intrinsics.detach(), "intrinsics"))
+        xyz, rgb, count, first, slot, pixel_slot, counters = _ops.voxel_cloud(depths, kinv, extrinsics, colors, keep, float(voxel_size), min_count, capacity, details)
+        rows, overflow, masked, invalid, out_of_range = (int(v) for v in counters[:5].tolist())  # (the one synchronisation: this is an export step)
+        if overflow > 0 or rows > capacity:
+            raise RuntimeError(f"flowmap_amd: voxel_point_cloud: the cloud does not fit capacity = {capacity}: {rows} voxels, {overflow} points found no "
+                               f"slot in the table; pass a larger capacity (at most the {f * h * w} pixels) or a larger voxel_size")
+        first, order = torch.sort(first[:rows])
+        xyz, count, slot = xyz[:rows][order], count[:rows][order], slot[:rows][order]
+        rgb = None if colors is None else rgb[:rows][order]
+        voxel_of = None
+        if details:
+            slots = 2
+            while slots < 2 * capacity:
+                slots *= 2
+            row_of_slot = torch.full((slots + 1,), -1, dtype=torch.int32, device=depths.device)  # (the last entry serves pixel_slot == −1)
+            row_of_slot[slot.long()] = torch.arange(rows, dtype=torch.int32, device=depths.device)
+            voxel_of = row_of_slot[pixel_slot.long()]
+    return VoxelCloud(xyz, rgb, count, first, {"masked": masked, "invalid": invalid, "out_of_range": out_of_range}, voxel_of, float(voxel_size))
 
 
 _PLY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),

@@ -135,3 +135,19 @@ class Model(nn.Module):
         -> RenderedViews.  It only reads: a LazyExtrinsics stays unevaluated."""
         colors = None if batch is None else batch.videos
         return render_views(model_output.depths, model_output.intrinsics, model_output.extrinsics, colors, **kw)
+
+    def point_cloud(self, model_output, batch=None, voxel_size=None, entry=0, **kw):
+        """export.voxel_point_cloud of batch entry ``entry`` of a ModelOutput's depths under its intrinsics and extrinsics, coloured with
+        ``batch.videos`` when a batch is given (``voxel_size``, ``keep`` (F,H,W), ``min_count``, ``capacity``, ``details`` as there)
+        -> VoxelCloud.  It only reads: a LazyExtrinsics stays unevaluated."""
+        from .. import _ops
+        from ..export import voxel_point_cloud
+        from .projection import LazyExtrinsics
+
+        if voxel_size is None:
+            raise ValueError("flowmap_amd: Model.point_cloud: voxel_size is required")
+        ext = model_output.extrinsics
+        if isinstance(ext, LazyExtrinsics):  # the chain for this call only: nothing is kept on the LazyExtrinsics
+            ext = ext._dense if ext._dense is not None else _ops.PoseChain.apply(ext._rel.detach())
+        colors = None if batch is None else batch.videos[entry]
+        return voxel_point_cloud(model_output.depths[entry].detach(), model_output.intrinsics[entry].detach(), ext[entry].detach(), colors, voxel_size, **kw)

@@ -11,6 +11,7 @@
   FocalSweep  what IntrinsicsSoftmin.residuals returns (likewise: the sweep keeps its error curve and per-candidate poses to itself)
   DepthConsistency  what projection.depth_consistency / Model.consistency return (likewise: the reference never compares its depth maps)
   RenderedViews  what projection.render_views / Model.render return (likewise: the reference never renders its reconstruction)
+  VoxelCloud  what export.voxel_point_cloud / Model.point_cloud return (likewise: the reference exports every pixel as a point)
 
 The reference's own dataclasses are accepted everywhere these are (duck typing): the
 drop-in never checks the class, only the attribute names.
@@ -237,3 +238,27 @@ class RenderedViews:
         held-out score."""
         total, count = self._error_sums(images, 2)
         return -10.0 * torch.log10(total / count)
+
+
+@dataclass
+class VoxelCloud:
+    """The world points of the depth maps merged per cell of a world-space grid — export.voxel_point_cloud / Model.point_cloud.  One
+    row per occupied voxel, in ascending ``first``; every field is a function of the set of points that fell into the voxel."""
+
+    xyz: Tensor  # (M, 3) float32: the centroid
+    rgb: Optional[Tensor]  # (M, 3) float32: the mean colour (clamped to [0, 1]); None without colors
+    count: Tensor  # (M,) int32: the points merged into the voxel
+    first: Tensor  # (M,) int64: the lowest linear index frame·H·W + pixel among them
+    dropped: dict  # Python ints: masked, invalid (depth not finite or <= 0, or a non-finite world coordinate), out_of_range
+    voxel_of: Optional[Tensor] = None  # (F, H, W) int32, with details=True: the row each pixel went to; −1 if dropped or filtered by min_count
+    voxel_size: Optional[float] = None
+
+    def __len__(self) -> int:
+        return int(self.xyz.shape[0])
+
+    def write_ply(self, path) -> None:
+        """export.write_ply of the centroids and mean colours (black without colours)."""
+        from .export import write_ply
+
+        xyz = self.xyz.detach().cpu().numpy()
+        write_ply(path, xyz, (torch.zeros_like(self.xyz) if self.rgb is None else self.rgb).detach().cpu().numpy())

@@ -47,9 +47,10 @@ extern "C" {
  * fm_alignment_residuals / fm_alignment_residual_workspace; the existing entries are unchanged; version 12: the softmin focal sweep per
  * pair — fm_focal_sweep; the existing entries are unchanged; version 13: the depth consistency across frame offsets —
  * fm_depth_consistency / fm_depth_consistency_blocks; the existing entries are unchanged; version 14: the rendered views —
- * fm_render_views / fm_render_views_workspace; the existing entries are unchanged).  A binding checks
+ * fm_render_views / fm_render_views_workspace; the existing entries are unchanged; version 15: the voxel-fused point cloud —
+ * fm_voxel_cloud / fm_voxel_cloud_workspace; the existing entries are unchanged).  A binding checks
  * fm_abi_version() == FM_ABI_VERSION when it loads the library. */
-#define FM_ABI_VERSION 14
+#define FM_ABI_VERSION 15
 int fm_abi_version(void);
 
 #define FM_STAT_STRIDE 16      /* doubles per pair in `stats` */
@@ -930,6 +931,39 @@ int fm_render_views_workspace(int batch, int views, int out_height, int out_widt
 int fm_render_views(const float* depth, const float* kinv, const float* ext, const float* colors, const float* view_k, const float* view_ext,
                     const int32_t* pairs, int n_pairs, int batch, int frames, int height, int width, int views, int out_height, int out_width,
                     int radius, float near, float background, float* color, float* out_depth, int32_t* source, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Voxel-fused point cloud (ABI version 15): the world points of the depth maps merged per cell of a world-space grid, in one pass over
+ * depth — no point cloud is formed.  Per pixel of frame i, linear index i·H·W + y·W + x:
+ *   world point: exactly what fm_world_points writes for it, to the bit (fm_math.h: world_point_at);
+ *   dropped as `masked` where keep is 0; else as `invalid` where the depth is not finite or <= 0 or a world coordinate is not finite;
+ *   per axis, with inv = (float)(1.0 / voxel_size): t = x·inv (one fp32 multiply), cell = floorf(t), frac = t − cell; dropped as
+ *   `out_of_range` unless −2^20 <= cell < 2^20 on all three axes; key = the cells biased by 2^20, 21 bits each, x highest.
+ * A voxel accumulates INTEGERS only: Σ min((uint32)(frac·2^20), 2^20 − 1) per axis, Σ (uint32)(clamp(c,0,1)·2^16) per colour channel (a
+ * NaN counts as 0), the count, the minimum linear index — so the result is a function of the set of points, never of arrival order.
+ *   xyz = (cell + (Σ/count + 0.5)/2^20)·voxel_size,  rgb = Σ/count/2^16: fp64, rounded once to fp32 (fm_math.h: voxel_finalize).
+ *
+ *   depth (F,H,W), kinv (F,3,3), ext (F,4,4) camera-to-world, colors (F,3,H,W) or NULL, keep (F,H,W) bytes or NULL: dense.
+ *   1 <= F <= 65535, H·W < 2^30, F·H·W < 2^31; voxel_size finite and > 0 with a finite, normal fp32 reciprocal; min_count >= 1;
+ *   1 <= capacity <= 2^28.
+ *   xyz (capacity,3), rgb (capacity,3; given exactly when colors is), count (capacity) int32, first (capacity) int64 — the voxel's lowest
+ *     linear index —, slot (capacity) int32 — the table slot of the row: rows [0, min(rows drawn, capacity)) are written, in NO particular
+ *     order (sort by `first`, which is unique per row); a voxel with count < min_count draws no row.
+ *   pixel_slot (F,H,W) int32 out or NULL: the table slot each pixel's point went to, −1 where it was dropped or found no slot.
+ *   counters: 8 DEVICE 8-byte words out, 8-byte aligned: [0] rows drawn (> capacity: the cloud did not fit), [1] points that found no
+ *     slot — the table was full: raise capacity —, [2] masked, [3] invalid, [4] out_of_range; [5..7] zero.
+ *   workspace: fm_voxel_cloud_workspace bytes, 64-byte aligned, contents unspecified on entry and on return: `slots` 64-byte records,
+ *     then `slots` 8-byte keys; slots = the smallest power of two >= 2·capacity, home slot = voxel_hash(key) & (slots − 1), linear probing.
+ * Launches: three memsets on the stream (records 0, keys all-ones, counters 0), ONE pass over depth (a workgroup 1024 consecutive pixels
+ * of one frame; one 16-byte depth load per thread when W % 4 == 0 and the base is aligned, else a scalar path with the same results): per
+ * live point a walk of the probe chain — a key load per slot, one 8-byte compare-and-swap only into an empty slot, never a wait — and 8
+ * no-return 8-byte atomics into ONE 64-byte record (5 without colours); then one thread per slot, one atomic per wave for the rows.
+ *
+ * fm_voxel_cloud_workspace: slots[0], bytes[0] (HOST longs) = the table's slots and the workspace size of a call with this capacity. */
+int fm_voxel_cloud_workspace(long capacity, long* slots, long* bytes);
+int fm_voxel_cloud(const float* depth, const float* kinv, const float* ext, const float* colors, const uint8_t* keep, int frames, int height,
+                   int width, double voxel_size, int min_count, long capacity, float* xyz, float* rgb, int32_t* count, int64_t* first,
+                   int32_t* slot, int32_t* pixel_slot, unsigned long long* counters, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
