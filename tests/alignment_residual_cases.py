@@ -26,7 +26,8 @@ import numpy as np
 import torch
 
 from conftest import assert_close, assert_close_or_reference_gap, load_golden, t
-from flow_residual_cases import inputs, ulp_distance
+from flow_residual_cases import inputs
+from operator_checks import HEIGHT, WIDTH, assert_training_untouched, same_tensors, train, ulp_distance
 from oracle import flowmap_oracle as orc
 
 TILE = 1024  # elements per workgroup (fm_alignment_residuals.hip: kAlignTile)
@@ -163,12 +164,8 @@ def check_terms(r, truth, ref32, what, win=slice(None)):
     return worst
 
 
-def same_fields(a, b, what=""):
-    for name in ("residual", "offset", "weight", "pair_sum", "pair_weight"):
-        x, y = getattr(a, name), getattr(b, name)
-        assert (x is None) == (y is None), f"{what}{name}"
-        if x is not None:
-            assert torch.equal(x, y), f"{what}{name}: not bit-equal (max |diff| {float((x.double() - y.double()).abs().max()):.3e})"
+def same_fields(a, b, what="", **kw):
+    same_tensors(a, b, ("residual", "offset", "weight", "pair_sum", "pair_weight"), what, **kw)
 
 
 # ---- case 1: reference parity --------------------------------------------------------------------------------------------------------------
@@ -370,19 +367,12 @@ def case_lazy_weights(dev, shape, how=None, sensitivity=100.0):
 
 
 def _train(dev, tracking, calls, fuse, steps=5):
-    """``steps`` optimisation steps (flow loss, with ``tracking`` the tracking loss and the tap exchange) with FusedAdam — ``fuse``: applying
-    the depth update inside the flow pass; ``calls``: ExtrinsicsProcrustes.residuals between forward and backward and again between the
-    steps.  (After flow_residual_cases._train.)"""
-    import cases
-    import flowmap_amd
-    from flowmap_amd import FusedAdam, _ops
-    from flowmap_amd.loss import LossFlow, LossFlowCfg, LossTracking, LossTrackingCfg
+    """operator_checks.train, 5 steps from step 0 after the warm-up; ``calls``: ExtrinsicsProcrustes.residuals between forward and backward
+    (a window on the fit's own indices, with offsets and weights) and again between the steps.  -> (the record, the PoseChain evaluations
+    of the run and whether the fit was asked for chained poses: ``_fm_extrinsics_wanted`` on the backward flows)."""
+    from flowmap_amd import _ops
     from flowmap_amd.model.extrinsics_procrustes import procrustes_indices
-    from flowmap_amd.model.projection import LazyExtrinsics
-    from helpers import mapping_cfg, to_tracks
 
-    min_bytes = _ops.options.tap_exchange_min_bytes
-    _ops.options.tap_exchange_min_bytes = 0
     chain_calls = [0]
     chain = _ops.PoseChain.apply
 
@@ -390,89 +380,38 @@ def _train(dev, tracking, calls, fuse, steps=5):
         chain_calls[0] += 1
         return chain(rel)
 
+    def mid(ns):
+        own = procrustes_indices(HEIGHT, WIDTH, ns.model.extrinsics.cfg.num_points, False, torch.device(dev))
+        return ns.model.extrinsics.residuals(ns.batch, ns.flows, ns.out, pairs=(1, 2), indices=own, offsets=True, weights=True)
+
+    after = lambda ns: ns.model.extrinsics.residuals(ns.batch, ns.flows, ns.out)  # noqa: E731
+    flows = []
     _ops.PoseChain.apply = staticmethod(counted_chain)
     try:
-        f, h, w = 5, 24, 32
-        model, batch, flows, _ = cases._small_problem(dev, f=f, h=h, w=w, tracking=False)
-        sc = orc.synth_scene(f, h, w, seed=21)
-        tracks = to_tracks(orc.synth_tracks(f, h, w, scene=sc, seed=21, interval=2, radius=2, grid=5), dev) if tracking else None
-        flow_fn = LossFlow(LossFlowCfg(0, 1000.0, "flow", mapping_cfg("huber")))
-        track_fn = LossTracking(LossTrackingCfg(0, 100.0, "tracking", mapping_cfg("huber")))
-        optimizer = FusedAdam(model.parameters(), lr=1e-3)
-        if fuse:
-            optimizer.fuse_depth_update(model.backbone.depth, max_touched_fraction=1.0)
-        focal = next(p for name, p in model.named_parameters() if name.endswith("focal_length"))
-        own = procrustes_indices(h, w, model.extrinsics.cfg.num_points, False, torch.device(dev))
-        # One forward + backward whose gradients are thrown away, in both runs, before anything is compared: the sparse fit's scatter plan is
-        # built when the same (indices, flows) come back a second time, and until it exists fm_procrustes_scatter adds into dL/ddepth with
-        # float atomics — two runs of that FIRST backward differ in the last bit of dL/ddepth where two taps share a pixel (DESIGN.md §4,
-        # "Determinism"), calls or no calls, and Adam would carry the bit into every later step.  No parameter moves here.
-        out = model(batch, flows, 0)
-        total = flow_fn(batch, flows, tracks, out, 0)
-        (total + track_fn(batch, flows, tracks, out, 0) if tracking else total).backward()
-        optimizer.zero_grad(set_to_none=True)
-        del out, total
-        before = dict(_ops.counters)
-        history, seen, lazy_kept = [], [], []
-        for step in range(steps):
-            optimizer.zero_grad(set_to_none=True)
-            out = model(batch, flows, step)
-            total = flow_fn(batch, flows, tracks, out, step)
-            if tracking:
-                total = total + track_fn(batch, flows, tracks, out, step)
-            if calls:
-                was_lazy = isinstance(out.extrinsics, LazyExtrinsics) and out.extrinsics._dense is None
-                seen.append(model.extrinsics.residuals(batch, flows, out, pairs=(1, 2), indices=own, offsets=True, weights=True))
-                if was_lazy:
-                    lazy_kept.append(out.extrinsics._dense is None)
-            total.backward()
-            history.append([total.detach().clone()] + [p.grad.detach().clone() for p in (model.backbone.depth, model.backbone.weights, focal)])
-            optimizer.step()
-            if calls:
-                seen.append(model.extrinsics.residuals(batch, flows, out))
-        moved = {key: value - before.get(key, 0) for key, value in _ops.counters.items()}
-        params = [p.detach().clone() for p in (model.backbone.depth, model.backbone.weights, focal)]
-        # (a note's name may end in the id() of the object it belongs to: dropped, the two runs build their own objects)
-        notes = sorted(key.rstrip("0123456789") for tensor in (flows.backward, model.backbone.depth, model.backbone.weights) for key in tensor.__dict__
-                       if key.startswith("_fm_"))
-        state = {"wanted": bool(flows.backward.__dict__.get("_fm_extrinsics_wanted", False)), "chain_calls": chain_calls[0],
-                 "in_pass": optimizer.counters.get("in_pass_updates", 0), "depth_version": model.backbone.depth._version, "notes": notes}
-        return history, params, moved, state, seen, lazy_kept
+        run = train(dev, tracking=tracking, fuse=fuse, steps=steps, first_step=0, warm_up=True, calls=(mid, after) if calls else None,
+                    prepare=lambda ns: flows.append(ns.flows))
     finally:
         _ops.PoseChain.apply = staticmethod(chain)
-        _ops.options.tap_exchange_min_bytes = min_bytes
-        flowmap_amd.set_lazy_surfaces(False)
+    return run, {"wanted": bool(flows[0].backward.__dict__.get("_fm_extrinsics_wanted", False)), "chain_calls": chain_calls[0]}
 
 
 def case_training_untouched(dev, tracking, fuse):
     """A flow (+ tracking, tap exchange on) run with FusedAdam (``fuse``: FusedAdam.fuse_depth_update), with and without two residuals()
-    calls per step: loss and every gradient of every step and the parameters at the end are bit-equal, the operator counters differ by
-    ``alignment_residuals`` alone, the same ``_fm_*`` notes sit on the flow, depth and weight tensors, no pose chain was evaluated for the
-    calls, and a LazyExtrinsics in the output is still unevaluated after a call.  (With the depth update inside the flow pass
-    ``depth.grad`` is defined at the sparse pixels of the other operators only — there dL/ddepth is compared through the depth parameter
-    it moved, and element for element in the run with the separate update.)"""
+    calls per step: operator_checks.assert_training_untouched with ``alignment_residuals`` the one counter that differs, no pose chain was
+    evaluated for the calls, and a flow-only step does hand out a LazyExtrinsics for the shared check to find unevaluated after a call."""
     steps = 5
-    plain = _train(dev, tracking, calls=False, fuse=fuse, steps=steps)
-    with_calls = _train(dev, tracking, calls=True, fuse=fuse, steps=steps)
-    for step, (a, b) in enumerate(zip(with_calls[0], plain[0])):
-        for x, y, what in zip(a, b, ("loss", "g_depth", "g_weights", "g_focal")):
-            if fuse and what == "g_depth":
-                continue
-            assert torch.equal(x, y), f"step {step}: {what} differs (max |diff| {float((x.double() - y.double()).abs().max()):.3e})"
-    for x, y, what in zip(with_calls[1], plain[1], ("depth", "weights", "focal")):
-        assert torch.equal(x, y), f"{what} after {steps} steps differs"
-    moved, base = with_calls[2], plain[2]
-    assert moved.pop("alignment_residuals") == 2 * steps and base.pop("alignment_residuals") == 0
-    assert moved == base, (moved, base)
-    assert with_calls[3] == plain[3], (with_calls[3], plain[3])
+    plain, chained = _train(dev, tracking, calls=False, fuse=fuse, steps=steps)
+    with_calls, chained_with_calls = _train(dev, tracking, calls=True, fuse=fuse, steps=steps)
+    _, base = assert_training_untouched(plain, with_calls, "alignment_residuals", 2 * steps)
+    assert chained_with_calls == chained, (chained_with_calls, chained)
     if not tracking:
-        assert plain[3]["chain_calls"] == 0 and not plain[3]["wanted"]  # a flow-only run never chains the poses, with the calls neither
-        assert with_calls[5] and all(with_calls[5]), "a LazyExtrinsics was evaluated by residuals()"
+        assert chained["chain_calls"] == 0 and not chained["wanted"]  # a flow-only run never chains the poses, with the calls neither
+        assert any(was for was, _ in with_calls.lazy_kept) and all(after for was, after in with_calls.lazy_kept if was), "a LazyExtrinsics was evaluated by residuals()"
     else:
         assert base["flow_tap_passes"] > 0  # the tap exchange really ran
-    for r in with_calls[4]:
+    for r in with_calls.seen:
         assert bool(torch.isfinite(r.residual).all()) and bool(torch.isfinite(r.pair_sum).all())
-    first, second = with_calls[4][0], with_calls[4][1]
+    first, second = with_calls.seen[0], with_calls.seen[1]
     assert first.first_pair == 1 and first.residual.shape == (1, 2, 60) and first.offset.shape == (1, 2, 60, 3) and second.residual.shape == (1, 4, 24, 32)
 
 

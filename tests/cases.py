@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from conftest import assert_close, assert_close_or_reference_gap, load_golden, maxerr, relerr, t
-from flowmap_amd import Tracks
+from flowmap_amd import Tracks, config
 from flowmap_amd.loss.mapping import get_mapping
 from flowmap_amd.model import procrustes as fp
 from flowmap_amd.model import projection as fm
@@ -525,14 +525,9 @@ def case_packed_inputs(dev, hw=(18, 28)):
 
     res = {}
     for use in (True, False):
-        _ops.options.packed_inputs = use
-        _ops.options.pack_on_first_sight = True  # (a single step: the loss would otherwise stream the reference layout both times)
         packs = _ops.counters["flow_packs"]
-        try:
+        with config.override(packed_inputs=use, pack_on_first_sight=True):  # (a single step: the loss would otherwise stream the reference layout both times)
             res[use] = run_ours(depth, wlogit, focal, oflows, (h, w), 100, device=dev)
-        finally:
-            _ops.options.packed_inputs = True
-            _ops.options.pack_on_first_sight = False
         # (on the host double `.to("cpu")` hands run_ours the very tensors packed above: the cached copy is then reused)
         assert _ops.counters["flow_packs"] - packs <= (1 if (use and w % 4 == 0) else 0)
     # identical arithmetic per residual; only the order of the float atomics differs run to run
@@ -912,11 +907,8 @@ def case_dense_procrustes(dev, h, w, flow_sigma, f=4):
     for name, idx, planned in (("tiled", None, False), ("tiled_planned", None, True), ("generic", torch.arange(h * w, device=dev), False)):
         d, kk, lg = (x.clone().to(dev).requires_grad_(True) for x in (depth, k, logits))
         fl_dev = flow.clone().to(dev)
-        _ops.options.dense_plan = planned
-        try:
+        with config.override(dense_plan=planned):
             t_bwd, t_fwd = _ops.ProcrustesFit.apply(d, kk, None, lg, fl_dev, idx, 100.0, 1)
-        finally:
-            _ops.options.dense_plan = None
         ((t_bwd * cot_b.to(dev)).sum() + (t_fwd * cot_f.to(dev)).sum()).backward()
         res[name] = (t_bwd.detach(), d.grad, lg.grad, kk.grad)
         assert ("_fm_dense_plan" in fl_dev.__dict__) == planned  # the fused pass (the default) builds no lists
@@ -996,85 +988,82 @@ def case_tap_exchange(dev):
         return {"sum": [lf + lt], "scaled": [2.0 * lf + 0.5 * lt], "flow_only": [lf], "track_only": [lt], "two_calls": [lf, lt]}[how]
 
     def run(exchange: bool, how: str, steps: int = 3, move_at=None, track_kind="huber"):
-        _ops.options.tap_exchange = exchange
-        model, batch, flows, _ = _small_problem(dev, f=f, h=h, w=w, tracking=False, seed=33)
-        tracks = to_tracks(otracks, dev)
-        flow_fn = LossFlow(LossFlowCfg(0, 1000.0, "flow", mapping_cfg("huber")))
-        track_fn = LossTracking(LossTrackingCfg(0, 100.0, "tracking", mapping_cfg(track_kind)))
-        results, sinks = [], []
-        for step in range(steps):
-            if move_at is not None and step == move_at:
-                with torch.no_grad():
-                    model.backbone.depth.mul_(1.01)  # the parameter moves (an optimiser the library does not know): the image is stale
-            model.zero_grad(set_to_none=True)
-            out = model(batch, flows, step)
-            lf = flow_fn(batch, flows, tracks, out, step)
-            lt = track_fn(batch, flows, tracks, out, step)
-            calls = roots(lf, lt, how)
-            for i, root in enumerate(calls):
-                root.backward(retain_graph=i + 1 < len(calls))
-            sinks.append(_ops.depth_sink(out.depths))
-            results.append([x.detach().clone() for x in (lf, lt, out.extrinsics, model.backbone.depth.grad, model.backbone.weights.grad,
-                                                         model.intrinsics.focal_length.grad)])
-        return results, sinks
+        with config.override(tap_exchange=exchange):
+            model, batch, flows, _ = _small_problem(dev, f=f, h=h, w=w, tracking=False, seed=33)
+            tracks = to_tracks(otracks, dev)
+            flow_fn = LossFlow(LossFlowCfg(0, 1000.0, "flow", mapping_cfg("huber")))
+            track_fn = LossTracking(LossTrackingCfg(0, 100.0, "tracking", mapping_cfg(track_kind)))
+            results, sinks = [], []
+            for step in range(steps):
+                if move_at is not None and step == move_at:
+                    with torch.no_grad():
+                        model.backbone.depth.mul_(1.01)  # the parameter moves (an optimiser the library does not know): the image is stale
+                model.zero_grad(set_to_none=True)
+                out = model(batch, flows, step)
+                lf = flow_fn(batch, flows, tracks, out, step)
+                lt = track_fn(batch, flows, tracks, out, step)
+                calls = roots(lf, lt, how)
+                for i, root in enumerate(calls):
+                    root.backward(retain_graph=i + 1 < len(calls))
+                sinks.append(_ops.depth_sink(out.depths))
+                results.append([x.detach().clone() for x in (lf, lt, out.extrinsics, model.backbone.depth.grad, model.backbone.weights.grad,
+                                                             model.intrinsics.focal_length.grad)])
+            return results, sinks
 
     names = ("loss_flow", "loss_tracking", "extrinsics", "g_depth", "g_wlogit", "g_focal")
-    min_bytes = _ops.options.tap_exchange_min_bytes
-    _ops.options.tap_exchange_min_bytes = 0  # (by default the exchange engages for depth tensors beyond the last-level cache only)
-    try:
-        for how in ("sum", "scaled", "flow_only", "track_only", "two_calls"):
+    with config.override(tap_exchange_min_bytes=0):  # (by default the exchange engages for depth tensors beyond the last-level cache only)
+        try:
+            for how in ("sum", "scaled", "flow_only", "track_only", "two_calls"):
+                before = dict(_ops.counters)
+                plain, _ = run(False, how)
+                assert _ops.counters["flow_tap_passes"] == before["flow_tap_passes"]
+                got, sinks = run(True, how)
+                assert _ops.counters["flow_tap_absorbs"] - before["flow_tap_absorbs"] == 2, (how, _ops.counters)  # steps 1 and 2
+                assert _ops.counters["track_tap_samples"] - before["track_tap_samples"] == 1, (how, _ops.counters)  # step 2 (the image exists after step 1)
+                free, launched = (sum(s.taps_settled()[i] for s in sinks) for i in (0, 1))
+                assert (free, launched) == {"sum": (2, 0), "scaled": (0, 2), "flow_only": (0, 2), "track_only": (0, 2), "two_calls": (0, 2)}[how], (how, free, launched)
+                for step, (a, b) in enumerate(zip(got, plain)):
+                    for x, y, what in zip(a, b, names):
+                        # same arithmetic per element; the absorbed gradient joins the flow pass's sum in another order (fp32 rounding of one add)
+                        err = float((x - y).abs().max())
+                        assert err <= 2e-6 * max(float(y.abs().max()), 1e-30), (how, step, what, err, float(y.abs().max()))
+                # the tracking part is really there (the comparison is not vacuous): dL/ddepth differs from the flow-only gradient at the taps
+                assert float((got[2][3] - run(False, "flow_only", steps=1)[0][0][3]).abs().max()) > 0 or how == "flow_only"
+            # a parameter that moved between the steps: the compact image is not sampled from (and the results still agree)
             before = dict(_ops.counters)
-            plain, _ = run(False, how)
-            assert _ops.counters["flow_tap_passes"] == before["flow_tap_passes"]
-            got, sinks = run(True, how)
-            assert _ops.counters["flow_tap_absorbs"] - before["flow_tap_absorbs"] == 2, (how, _ops.counters)  # steps 1 and 2
-            assert _ops.counters["track_tap_samples"] - before["track_tap_samples"] == 1, (how, _ops.counters)  # step 2 (the image exists after step 1)
-            free, launched = (sum(s.taps_settled()[i] for s in sinks) for i in (0, 1))
-            assert (free, launched) == {"sum": (2, 0), "scaled": (0, 2), "flow_only": (0, 2), "track_only": (0, 2), "two_calls": (0, 2)}[how], (how, free, launched)
+            plain, _ = run(False, "sum", steps=4, move_at=2)
+            got, _ = run(True, "sum", steps=4, move_at=2)
+            assert _ops.counters["track_tap_samples"] - before["track_tap_samples"] == 1, _ops.counters  # step 3 only (step 2 saw a moved parameter)
             for step, (a, b) in enumerate(zip(got, plain)):
                 for x, y, what in zip(a, b, names):
-                    # same arithmetic per element; the absorbed gradient joins the flow pass's sum in another order (fp32 rounding of one add)
                     err = float((x - y).abs().max())
-                    assert err <= 2e-6 * max(float(y.abs().max()), 1e-30), (how, step, what, err, float(y.abs().max()))
-            # the tracking part is really there (the comparison is not vacuous): dL/ddepth differs from the flow-only gradient at the taps
-            assert float((got[2][3] - run(False, "flow_only", steps=1)[0][0][3]).abs().max()) > 0 or how == "flow_only"
-        # a parameter that moved between the steps: the compact image is not sampled from (and the results still agree)
-        before = dict(_ops.counters)
-        plain, _ = run(False, "sum", steps=4, move_at=2)
-        got, _ = run(True, "sum", steps=4, move_at=2)
-        assert _ops.counters["track_tap_samples"] - before["track_tap_samples"] == 1, _ops.counters  # step 3 only (step 2 saw a moved parameter)
-        for step, (a, b) in enumerate(zip(got, plain)):
-            for x, y, what in zip(a, b, names):
-                err = float((x - y).abs().max())
-                assert err <= 2e-6 * max(float(y.abs().max()), 1e-30), ("moved", step, what, err)
-        # an edit behind the version counter (`param.data...`): the flow pass finds the image the tracking loss sampled stale — loudly
-        _ops.options.tap_exchange = True
-        model, batch, flows, _ = _small_problem(dev, f=f, h=h, w=w, tracking=False, seed=33)
-        tracks = to_tracks(orc.synth_tracks(f, h, w, scene=sc, seed=34, interval=2, radius=2, grid=6), dev)
-        flow_fn = LossFlow(LossFlowCfg(0, 1000.0, "flow", mapping_cfg("huber")))
-        track_fn = LossTracking(LossTrackingCfg(0, 100.0, "tracking", mapping_cfg("huber")))
-        raised = False
-        for step in range(3):
-            if step == 2:
-                model.backbone.depth.data.mul_(1.01)
-            model.zero_grad(set_to_none=True)
-            out = model(batch, flows, step)
-            try:
-                total = flow_fn(batch, flows, tracks, out, step) + track_fn(batch, flows, tracks, out, step)
-            except RuntimeError as exc:
-                raised = "version counter" in str(exc)
-                break
-            total.backward()
-        assert raised
-        # another robust kernel on the tracking side (the exchange does not depend on it)
-        plain, _ = run(False, "sum", track_kind="l1")
-        got, _ = run(True, "sum", track_kind="l1")
-        for x, y, what in zip(got[-1], plain[-1], names):
-            assert float((x - y).abs().max()) <= 2e-6 * max(float(y.abs().max()), 1e-30), ("l1", what)
-    finally:
-        _ops.options.tap_exchange = True
-        _ops.options.tap_exchange_min_bytes = min_bytes
-        flowmap_amd.set_lazy_surfaces(False)
+                    assert err <= 2e-6 * max(float(y.abs().max()), 1e-30), ("moved", step, what, err)
+            # an edit behind the version counter (`param.data...`): the flow pass finds the image the tracking loss sampled stale — loudly
+            with config.override(tap_exchange=True):
+                model, batch, flows, _ = _small_problem(dev, f=f, h=h, w=w, tracking=False, seed=33)
+                tracks = to_tracks(orc.synth_tracks(f, h, w, scene=sc, seed=34, interval=2, radius=2, grid=6), dev)
+                flow_fn = LossFlow(LossFlowCfg(0, 1000.0, "flow", mapping_cfg("huber")))
+                track_fn = LossTracking(LossTrackingCfg(0, 100.0, "tracking", mapping_cfg("huber")))
+                raised = False
+                for step in range(3):
+                    if step == 2:
+                        model.backbone.depth.data.mul_(1.01)
+                    model.zero_grad(set_to_none=True)
+                    out = model(batch, flows, step)
+                    try:
+                        total = flow_fn(batch, flows, tracks, out, step) + track_fn(batch, flows, tracks, out, step)
+                    except RuntimeError as exc:
+                        raised = "version counter" in str(exc)
+                        break
+                    total.backward()
+                assert raised
+            # another robust kernel on the tracking side (the exchange does not depend on it)
+            plain, _ = run(False, "sum", track_kind="l1")
+            got, _ = run(True, "sum", track_kind="l1")
+            for x, y, what in zip(got[-1], plain[-1], names):
+                assert float((x - y).abs().max()) <= 2e-6 * max(float(y.abs().max()), 1e-30), ("l1", what)
+        finally:
+            flowmap_amd.set_lazy_surfaces(False)
 
 
 def case_step_torch_ops(dev):
@@ -1092,35 +1081,34 @@ def case_step_torch_ops(dev):
         from flowmap_amd import _ops
         from flowmap_amd._lib import torch_ops
 
-        try:
-            _ops.options.unit_seed = tracking is not None  # (None: the plain-tensor path, flow only)
-            model, batch, flows, loss_of = _small_problem(dev, tracking=bool(tracking))
+        with config.override(unit_seed=tracking is not None):  # (None: the plain-tensor path, flow only)
+            try:
+                model, batch, flows, loss_of = _small_problem(dev, tracking=bool(tracking))
 
-            def step():
-                model.zero_grad(set_to_none=True)
-                loss = loss_of(model(batch, flows, 0))
-                assert (type(loss) is _ops.RootLoss) == (tracking is not None)
-                loss.backward()
+                def step():
+                    model.zero_grad(set_to_none=True)
+                    loss = loss_of(model(batch, flows, 0))
+                    assert (type(loss) is _ops.RootLoss) == (tracking is not None)
+                    loss.backward()
 
-            for _ in range(3):  # plans, packed inputs, arenas exist from the third step on
-                step()
-            seen = {}
-            known_unit = torch_ops().unit_seed_uses()
+                for _ in range(3):  # plans, packed inputs, arenas exist from the third step on
+                    step()
+                seen = {}
+                known_unit = torch_ops().unit_seed_uses()
 
-            class Trace(TorchDispatchMode):
-                def __torch_dispatch__(self, func, types, args=(), kwargs=None):
-                    name = str(func)
-                    if not any(q in name for q in quiet):
-                        seen[name] = seen.get(name, 0) + 1
-                    return func(*args, **(kwargs or {}))
+                class Trace(TorchDispatchMode):
+                    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+                        name = str(func)
+                        if not any(q in name for q in quiet):
+                            seen[name] = seen.get(name, 0) + 1
+                        return func(*args, **(kwargs or {}))
 
-            with Trace():
-                step()
-            assert seen == allowed, (tracking, seen)
-            assert torch_ops().unit_seed_uses() - known_unit == int(tracking is not None)  # the flow loss's node knew its seed on the host
-        finally:
-            _ops.options.unit_seed = True
-            flowmap_amd.set_lazy_surfaces(False)
+                with Trace():
+                    step()
+                assert seen == allowed, (tracking, seen)
+                assert torch_ops().unit_seed_uses() - known_unit == int(tracking is not None)  # the flow loss's node knew its seed on the host
+            finally:
+                flowmap_amd.set_lazy_surfaces(False)
 
 
 def _grads(model):
@@ -1222,10 +1210,9 @@ def case_root_loss(dev):
 
         for _ in range(3):
             grads_of(lambda loss: loss.backward())
-        _ops.options.unit_seed = False
-        plain = grads_of(lambda loss: loss.backward())
-        plain3 = grads_of(lambda loss: (3.0 * loss).backward())
-        _ops.options.unit_seed = True
+        with config.override(unit_seed=False):
+            plain = grads_of(lambda loss: loss.backward())
+            plain3 = grads_of(lambda loss: (3.0 * loss).backward())
 
         def same(got, want, what):
             for a, b in zip(got, want):
@@ -1280,7 +1267,6 @@ def case_root_loss(dev):
         with torch.no_grad():
             assert type(loss_of(model(batch, flows, 0))) is torch.Tensor  # nothing to seed without a graph
     finally:
-        _ops.options.unit_seed = True
         flowmap_amd.set_lazy_surfaces(False)
 
 
@@ -1289,19 +1275,18 @@ def case_grad_arena(dev):
     step; one storage reused from the first planned step on; a gradient that is kept (accumulation without
     zero_grad) or edited in place (clipping) is never written under — the step falls back to a fresh buffer."""
     import flowmap_amd
-    from flowmap_amd import _ops
 
     try:
         history = {}
         for arena in (False, True):
-            _ops.options.grad_arena = arena
-            model, batch, flows, loss_of = _small_problem(dev, tracking=False)
-            steps = []
-            for _ in range(5):  # step 1: atomics into zeros; step 2 builds the plan; from then on the arena
-                model.zero_grad(set_to_none=True)
-                loss_of(model(batch, flows, 0)).backward()
-                steps.append(_grads(model))
-            history[arena] = (steps, model)
+            with config.override(grad_arena=arena):
+                model, batch, flows, loss_of = _small_problem(dev, tracking=False)
+                steps = []
+                for _ in range(5):  # step 1: atomics into zeros; step 2 builds the plan; from then on the arena
+                    model.zero_grad(set_to_none=True)
+                    loss_of(model(batch, flows, 0)).backward()
+                    steps.append(_grads(model))
+                history[arena] = (steps, model)
         for step, (a, b) in enumerate(zip(history[False][0], history[True][0])):
             for x, y, what in zip(a, b, ("g_depth", "g_weights", "g_focal")):
                 assert_close(y, x, 2e-5, abs_=1e-7, what=f"{what} step {step}")
@@ -1330,7 +1315,6 @@ def case_grad_arena(dev):
         assert arena.refilled() == refills + 1
         assert_close(model.backbone.weights.grad, once[1], 2e-5, abs_=1e-7, what="g_weights after an in-place edit")
     finally:
-        _ops.options.grad_arena = True
         flowmap_amd.set_lazy_surfaces(False)
 
 
@@ -1435,42 +1419,40 @@ def case_in_pass_adam(dev, steps=40, track_after=6, lr=1e-3, softmin=False, exch
     trajectories, engaged = {}, 0
     # ``exchange``: with the tap exchange forced on at this size — once the tracking loss runs, the flow pass absorbs its gradient, updates its
     # taps in the pass like any other pixel, and the next evaluation samples the image the update left (around the Procrustes pixels)
-    min_bytes, counted = _ops.options.tap_exchange_min_bytes, dict(_ops.counters)
-    _ops.options.tap_exchange_min_bytes = 0 if exchange else 1 << 60
+    counted = dict(_ops.counters)
     # softmin: the reference's default intrinsics (config/model/intrinsics/softmin.yaml) — the sweep reads random pixels of
     # frames 0 / 1, new every step, then hands over to a regressed focal length; both phases and the hand-over are crossed
     intrinsics = IntrinsicsSoftminCfg("softmin", 200, 0.5, 2.0, 8, RegressionCfg(steps // 2, 5)) if softmin else None
-    try:
-        for mode in ("torch", "fused", "in_pass", "fused_dense"):
-            torch.manual_seed(7)  # the sweep draws its pixels from torch's CPU generator
-            _ops.options.grad_arena = mode != "fused_dense"  # fused_dense: fresh zeros for dL/dweights, dense update of the logits
-            model, batch, flows, _ = _small_problem(dev, f=f, h=h, w=w, tracking=False, intrinsics=intrinsics)
-            sc = orc.synth_scene(f, h, w, seed=21)
-            tracks = to_tracks(orc.synth_tracks(f, h, w, scene=sc, seed=21, interval=2, radius=2, grid=5), dev)
-            flow_fn = LossFlow(LossFlowCfg(0, 1000.0, "flow", mapping_cfg("huber")))
-            track_fn = LossTracking(LossTrackingCfg(track_after, 100.0, "tracking", mapping_cfg("huber")))
-            optimizer = torch.optim.Adam(model.parameters(), lr=lr) if mode == "torch" else FusedAdam(model.parameters(), lr=lr)
-            if mode == "in_pass":
-                optimizer.fuse_depth_update(model.backbone.depth, max_touched_fraction=1.0)
-            history = []
-            for step in range(steps):
-                optimizer.zero_grad(set_to_none=True)
-                before = model.backbone.depth.detach().clone()
-                out = model(batch, flows, step)
-                total = flow_fn(batch, flows, tracks, out, step)
-                moved = mode == "in_pass" and not torch.equal(before, model.backbone.depth.detach())
-                engaged += int(moved)
-                total = total + track_fn(batch, flows, tracks, out, step)
-                total.backward()
-                optimizer.step()
-                focal = next(p for name, p in model.named_parameters() if name.endswith("focal_length"))
-                history.append([p.detach().clone() for p in (model.backbone.depth, model.backbone.weights, focal)]
-                               + [total.detach().clone()])
-            trajectories[mode] = (history, optimizer, model)
-    finally:
-        flowmap_amd.set_lazy_surfaces(False)
-        _ops.options.grad_arena = True
-        _ops.options.tap_exchange_min_bytes = min_bytes
+    with config.override(tap_exchange_min_bytes=0 if exchange else 1 << 60):
+        try:
+            for mode in ("torch", "fused", "in_pass", "fused_dense"):
+                torch.manual_seed(7)  # the sweep draws its pixels from torch's CPU generator
+                with config.override(grad_arena=mode != "fused_dense"):  # fused_dense: fresh zeros for dL/dweights, dense update of the logits
+                    model, batch, flows, _ = _small_problem(dev, f=f, h=h, w=w, tracking=False, intrinsics=intrinsics)
+                    sc = orc.synth_scene(f, h, w, seed=21)
+                    tracks = to_tracks(orc.synth_tracks(f, h, w, scene=sc, seed=21, interval=2, radius=2, grid=5), dev)
+                    flow_fn = LossFlow(LossFlowCfg(0, 1000.0, "flow", mapping_cfg("huber")))
+                    track_fn = LossTracking(LossTrackingCfg(track_after, 100.0, "tracking", mapping_cfg("huber")))
+                    optimizer = torch.optim.Adam(model.parameters(), lr=lr) if mode == "torch" else FusedAdam(model.parameters(), lr=lr)
+                    if mode == "in_pass":
+                        optimizer.fuse_depth_update(model.backbone.depth, max_touched_fraction=1.0)
+                    history = []
+                    for step in range(steps):
+                        optimizer.zero_grad(set_to_none=True)
+                        before = model.backbone.depth.detach().clone()
+                        out = model(batch, flows, step)
+                        total = flow_fn(batch, flows, tracks, out, step)
+                        moved = mode == "in_pass" and not torch.equal(before, model.backbone.depth.detach())
+                        engaged += int(moved)
+                        total = total + track_fn(batch, flows, tracks, out, step)
+                        total.backward()
+                        optimizer.step()
+                        focal = next(p for name, p in model.named_parameters() if name.endswith("focal_length"))
+                        history.append([p.detach().clone() for p in (model.backbone.depth, model.backbone.weights, focal)]
+                                       + [total.detach().clone()])
+                    trajectories[mode] = (history, optimizer, model)
+        finally:
+            flowmap_amd.set_lazy_surfaces(False)
     if exchange:
         tracked_steps = steps - track_after
         # per mode: the first tracked step runs in the plain order, every later one ahead of the flow pass; with the in-pass update the image
@@ -1539,50 +1521,48 @@ def case_in_pass_adam_exchange_unequal_upstreams(dev):
     from helpers import to_tracks
 
     f, h, w = 5, 24, 32
-    min_bytes = _ops.options.tap_exchange_min_bytes
-    _ops.options.tap_exchange_min_bytes = 0
-    try:
-        sc = orc.synth_scene(f, h, w, seed=21)
-        tracks = to_tracks(orc.synth_tracks(f, h, w, scene=sc, seed=21, interval=2, radius=2, grid=5), dev)
-        other = to_tracks(orc.synth_tracks(f, h, w, scene=sc, seed=5, interval=3, radius=1, grid=4), dev)
+    with config.override(tap_exchange_min_bytes=0):
+        try:
+            sc = orc.synth_scene(f, h, w, seed=21)
+            tracks = to_tracks(orc.synth_tracks(f, h, w, scene=sc, seed=21, interval=2, radius=2, grid=5), dev)
+            other = to_tracks(orc.synth_tracks(f, h, w, scene=sc, seed=5, interval=3, radius=1, grid=4), dev)
 
-        def loop(factor, steps, mode, second=False):
-            model, batch, flows, _ = _small_problem(dev, f=f, h=h, w=w, tracking=False)
-            flow_fn = LossFlow(LossFlowCfg(0, 1000.0, "flow", mapping_cfg("huber")))
-            track_fn = LossTracking(LossTrackingCfg(0, 100.0, "tracking", mapping_cfg("huber")))
-            second_fn = LossTracking(LossTrackingCfg(0, 50.0, "tracking", mapping_cfg("huber"))) if second else None
-            optimizer = torch.optim.Adam(model.parameters(), lr=1e-3) if mode == "torch" else FusedAdam(model.parameters(), lr=1e-3)
-            if mode == "in_pass":
-                optimizer.fuse_depth_update(model.backbone.depth, max_touched_fraction=1.0)
-                optimizer.verify_unit_upstream_every = 1
-            absorbed = _ops.counters["flow_tap_absorbs"]
-            for step in range(steps):
-                optimizer.zero_grad(set_to_none=True)
-                out = model(batch, flows, step)
-                total = flow_fn(batch, flows, tracks, out, step)
-                tracked = track_fn(batch, flows, tracks, out, step)
-                total = total + (tracked if factor == 1.0 else factor * tracked)
-                if second_fn is not None:
-                    total = total + second_fn(batch, flows, other, out, step)
-                total.backward()
-                optimizer.step()
-            return model.backbone.depth.detach().clone(), optimizer, _ops.counters["flow_tap_absorbs"] - absorbed
+            def loop(factor, steps, mode, second=False):
+                model, batch, flows, _ = _small_problem(dev, f=f, h=h, w=w, tracking=False)
+                flow_fn = LossFlow(LossFlowCfg(0, 1000.0, "flow", mapping_cfg("huber")))
+                track_fn = LossTracking(LossTrackingCfg(0, 100.0, "tracking", mapping_cfg("huber")))
+                second_fn = LossTracking(LossTrackingCfg(0, 50.0, "tracking", mapping_cfg("huber"))) if second else None
+                optimizer = torch.optim.Adam(model.parameters(), lr=1e-3) if mode == "torch" else FusedAdam(model.parameters(), lr=1e-3)
+                if mode == "in_pass":
+                    optimizer.fuse_depth_update(model.backbone.depth, max_touched_fraction=1.0)
+                    optimizer.verify_unit_upstream_every = 1
+                absorbed = _ops.counters["flow_tap_absorbs"]
+                for step in range(steps):
+                    optimizer.zero_grad(set_to_none=True)
+                    out = model(batch, flows, step)
+                    total = flow_fn(batch, flows, tracks, out, step)
+                    tracked = track_fn(batch, flows, tracks, out, step)
+                    total = total + (tracked if factor == 1.0 else factor * tracked)
+                    if second_fn is not None:
+                        total = total + second_fn(batch, flows, other, out, step)
+                    total.backward()
+                    optimizer.step()
+                return model.backbone.depth.detach().clone(), optimizer, _ops.counters["flow_tap_absorbs"] - absorbed
 
-        # equal upstreams: clean, and the pass did absorb
-        _, optimizer, absorbed = loop(1.0, 6, "in_pass")
-        assert absorbed >= 3 and optimizer.counters["in_pass_updates"] >= 4
-        # unequal upstreams: loud, not silently wrong
-        with pytest.raises(RuntimeError, match="unscaled"):
-            loop(3.0, 6, "in_pass")
-        # two tracking losses with their own track sets on one depth: the exchange (one tap set, one absorbed gradient per parameter) switches
-        # itself off for that parameter, both losses' pixels stay in the element list, the in-pass update still runs
-        d_ref, _, _ = loop(1.0, 8, "torch", second=True)
-        d_ours, optimizer, absorbed = loop(1.0, 8, "in_pass", second=True)
-        assert absorbed == 0 and optimizer.counters["in_pass_updates"] >= 5
-        assert float((d_ours - d_ref).abs().max()) <= 4e-6 * float(d_ref.abs().max()), float((d_ours - d_ref).abs().max())
-    finally:
-        flowmap_amd.set_lazy_surfaces(False)
-        _ops.options.tap_exchange_min_bytes = min_bytes
+            # equal upstreams: clean, and the pass did absorb
+            _, optimizer, absorbed = loop(1.0, 6, "in_pass")
+            assert absorbed >= 3 and optimizer.counters["in_pass_updates"] >= 4
+            # unequal upstreams: loud, not silently wrong
+            with pytest.raises(RuntimeError, match="unscaled"):
+                loop(3.0, 6, "in_pass")
+            # two tracking losses with their own track sets on one depth: the exchange (one tap set, one absorbed gradient per parameter) switches
+            # itself off for that parameter, both losses' pixels stay in the element list, the in-pass update still runs
+            d_ref, _, _ = loop(1.0, 8, "torch", second=True)
+            d_ours, optimizer, absorbed = loop(1.0, 8, "in_pass", second=True)
+            assert absorbed == 0 and optimizer.counters["in_pass_updates"] >= 5
+            assert float((d_ours - d_ref).abs().max()) <= 4e-6 * float(d_ref.abs().max()), float((d_ours - d_ref).abs().max())
+        finally:
+            flowmap_amd.set_lazy_surfaces(False)
 
 
 def case_in_pass_adam_refusals(dev):

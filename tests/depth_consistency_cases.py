@@ -28,7 +28,7 @@ import math
 import torch
 
 from conftest import assert_close_or_reference_gap, load_golden, relerr, t
-from flow_residual_cases import ulp_distance
+from operator_checks import assert_training_untouched, c_entry_refuses, gate_pair, host_tensor_refused, same_tensors, train, ulp_distance, window_rows
 from oracle import flowmap_oracle as orc
 
 T = 1024  # pixels per workgroup (fm_residual_args.h: kDepthConsTile)
@@ -73,14 +73,6 @@ def windows_of(frames):
     if frames <= 2:
         return [None, (0, 1), (frames - 1, 1)]
     return [None, (0, 1), (frames - 1, 1), slice(1, max(2, frames - 1))]
-
-
-def window_rows(window, frames):
-    if window is None:
-        return slice(0, frames)
-    if isinstance(window, slice):
-        return slice(*window.indices(frames)[:2])
-    return slice(window[0], window[0] + window[1])
 
 
 # ---- the oracle's composition ----------------------------------------------------------------------------------------------------------------
@@ -158,13 +150,6 @@ def check_fields(r, truth, ref32, what, rows=slice(None), fields=FIELDS, code_tr
     return worst
 
 
-def gate_pair(a, b, gap, what):
-    """Two fp32 evaluations of one quantity against each other: max(1e-4, 2 x the fp32-to-fp64 gap of that quantity)."""
-    e = relerr(a, b)
-    assert e <= max(1e-4, 2.0 * gap), f"{what}: rel err {e:.3e} > max(1e-4, 2 x fp32-reference gap {gap:.3e})"
-    return e
-
-
 # ---- plumbing -----------------------------------------------------------------------------------------------------------------------------
 
 
@@ -179,13 +164,8 @@ def run(name, dev, x=None, **kw):
 MAPS = ("error", "code", "positions", "reprojected", "sampled", "support", "frame_sum", "frame_valid")
 
 
-def same_fields(a, b, what="", rows=None):
-    for name in MAPS:
-        x, y = getattr(a, name), getattr(b, name)
-        assert (x is None) == (y is None), f"{what}{name}"
-        if x is not None:
-            y = y if rows is None else y[:, rows]
-            assert x.shape == y.shape and torch.equal(x, y), f"{what}{name}: not bit-equal"
+def same_fields(a, b, what="", **kw):
+    same_tensors(a, b, MAPS, what, **kw)
 
 
 def check_layout(r, name, dev, count=None, first=0, details=True, tolerance=True, sums=True):
@@ -424,22 +404,12 @@ def case_c_entries_refuse(lib, what):
 
     from flowmap_amd import _lib
 
-    fn = lib.fm_depth_consistency
-    fn.argtypes, fn.restype = _lib.SIGNATURES["fm_depth_consistency"], ctypes.c_int
-    raw = ctypes.create_string_buffer(4096 + 64)  # what the non-null pointers point at: host memory, never dereferenced
-    address = (ctypes.addressof(raw) + 63) & ~63
-    for change in C_REFUSED:
-        nulls = change == "nulls"
-        change = {} if nulls else change
-        held = (ctypes.c_int32 * 8)(*(list(change.get("offsets") or (-1, 2)) + [0] * 6)[:8])
-        args = []
-        for param, kind in zip(C_PARAMS, _lib.SIGNATURES["fm_depth_consistency"], strict=True):
-            if kind is ctypes.c_void_p:
-                null = nulls or param == "stream" or (param in change and change[param] is None)
-                args.append(None if null else (ctypes.cast(held, ctypes.c_void_p) if param == "offsets" else address))
-            else:
-                args.append({**C_VALID, **{k: v for k, v in change.items() if k != "offsets"}}[param])
-        assert fn(*args) == 1, f"{what}: fm_depth_consistency did not refuse ({'all pointers null' if nulls else change})"
+    def pointer(param, change, address):  # (the entry reads ``offsets`` on the host to check them: a real array of eight)
+        if param != "offsets":
+            return address
+        return ctypes.cast((ctypes.c_int32 * 8)(*(list(change.get("offsets") or (-1, 2)) + [0] * 6)[:8]), ctypes.c_void_p)
+
+    c_entry_refuses(lib, what, "fm_depth_consistency", C_PARAMS, C_VALID, C_REFUSED, pointer)
     size = lib.fm_depth_consistency_blocks
     size.argtypes, size.restype = _lib.SIGNATURES["fm_depth_consistency_blocks"], ctypes.c_int
     out = ctypes.c_int(-1)
@@ -451,101 +421,27 @@ def case_c_entries_refuse(lib, what):
 
 
 def case_host_tensor_refused():
-    """Without the test double and without install(), host tensors are refused by name."""
-    import pytest
-
-    from flowmap_amd import _lib
-
-    _lib.set_library_for_testing(None)
-    with pytest.raises(RuntimeError, match="flowmap_amd: depth_consistency: tensors are on cpu.*no CPU fallback"):
-        run("tiny", "cpu")
+    host_tensor_refused(lambda: run("tiny", "cpu"), "flowmap_amd: depth_consistency: tensors are on cpu.*no CPU fallback")
 
 
 # ---- check 7: training is left alone -----------------------------------------------------------------------------------------------------------
 
 
-def _train(dev, tracking, fuse, calls, steps=3):
-    """One discarded forward + backward (until the sparse fit's scatter plan exists its first backward adds with float atomics), then
-    ``steps`` optimisation steps (flow loss, with ``tracking`` the tracking loss) with FusedAdam — ``fuse``: the depth update inside the
-    flow pass; ``calls``: Model.consistency between forward and backward (a window, details, a tolerance) and between the steps."""
-    import cases
-    import flowmap_amd
-    from flowmap_amd import FusedAdam, _ops
-    from flowmap_amd.loss import LossFlow, LossFlowCfg, LossTracking, LossTrackingCfg
-    from flowmap_amd.model.projection import LazyExtrinsics
-    from helpers import mapping_cfg, to_tracks
-
-    min_bytes = _ops.options.tap_exchange_min_bytes
-    _ops.options.tap_exchange_min_bytes = 0
-    try:
-        f, h, w = 5, 24, 32
-        model, batch, flows, _ = cases._small_problem(dev, f=f, h=h, w=w, tracking=False)
-        sc = orc.synth_scene(f, h, w, seed=21)
-        tracks = to_tracks(orc.synth_tracks(f, h, w, scene=sc, seed=21, interval=2, radius=2, grid=5), dev) if tracking else None
-        flow_fn = LossFlow(LossFlowCfg(0, 1000.0, "flow", mapping_cfg("huber")))
-        track_fn = LossTracking(LossTrackingCfg(0, 100.0, "tracking", mapping_cfg("huber")))
-        optimizer = FusedAdam(model.parameters(), lr=1e-3)
-        if fuse:
-            optimizer.fuse_depth_update(model.backbone.depth, max_touched_fraction=1.0)
-        model.train()
-
-        def forward_loss(step):
-            out = model(batch, flows, step)
-            total = flow_fn(batch, flows, tracks, out, step)
-            return out, (total + track_fn(batch, flows, tracks, out, step) if tracking else total)
-
-        out, total = forward_loss(0)
-        total.backward()
-        optimizer.zero_grad(set_to_none=True)
-        del out, total
-        before = dict(_ops.counters)
-        history, seen, lazy_kept = [], [], []
-        for step in range(1, steps + 1):
-            optimizer.zero_grad(set_to_none=True)
-            out, total = forward_loss(step)
-            if calls:
-                was_lazy = isinstance(out.extrinsics, LazyExtrinsics) and out.extrinsics._dense is None
-                seen.append(model.consistency(out, offsets=(-2, -1, 1, 2), frames=(1, 3), details=True, tolerance=0.05))
-                lazy_kept.append((was_lazy, isinstance(out.extrinsics, LazyExtrinsics) and out.extrinsics._dense is None))
-            total.backward()
-            depth_grad = model.backbone.depth.grad
-            history.append([total.detach().clone(), None if (fuse or depth_grad is None) else depth_grad.detach().clone(), model.backbone.weights.grad.detach().clone()])
-            optimizer.step()
-            if calls:
-                seen.append(model.consistency(out))
-        moved = {key: value - before.get(key, 0) for key, value in _ops.counters.items()}
-        params = [p.detach().clone() for p in model.parameters()]
-        notes = sorted(key.rstrip("0123456789") for tensor in (flows.backward, model.backbone.depth, model.backbone.weights) for key in tensor.__dict__
-                       if key.startswith("_fm_"))
-        return history, params, moved, notes, seen, lazy_kept
-    finally:
-        _ops.options.tap_exchange_min_bytes = min_bytes
-        flowmap_amd.set_lazy_surfaces(False)
-
-
 def case_training_untouched(dev, tracking, fuse):
-    """Two identical runs of three steps, with and without consistency() calls: the loss and the gradients of every step and every parameter
-    after the last are bit-equal, the operator counters differ by ``depth_consistency`` alone, the same ``_fm_*`` notes sit on the flow,
-    depth and weight tensors, and a LazyExtrinsics handed in is still unevaluated afterwards."""
+    """operator_checks.train, 3 steps from step 1 after the warm-up, with and without Model.consistency between forward and backward (a
+    window, details, a tolerance) and between the steps: operator_checks.assert_training_untouched with ``depth_consistency`` the one
+    counter that differs — a LazyExtrinsics handed in is still unevaluated afterwards, and a flow-only step does hand one in."""
     steps = 3
-    plain = _train(dev, tracking, fuse, calls=False, steps=steps)
-    with_calls = _train(dev, tracking, fuse, calls=True, steps=steps)
-    for step, (a, b) in enumerate(zip(with_calls[0], plain[0])):
-        for x, y, what in zip(a, b, ("loss", "g_depth", "g_weights")):
-            assert (x is None) == (y is None)
-            if x is not None:
-                assert torch.equal(x, y), f"step {step}: {what} differs (max |diff| {float((x.double() - y.double()).abs().max()):.3e})"
-    assert len(with_calls[1]) == len(plain[1]) and all(torch.equal(x, y) for x, y in zip(with_calls[1], plain[1])), "the parameters after the last step differ"
-    moved, base = with_calls[2], plain[2]
-    assert moved.pop("depth_consistency") == 2 * steps and base.pop("depth_consistency") == 0
-    assert moved == base, (moved, base)
-    assert with_calls[3] == plain[3], (with_calls[3], plain[3])
-    assert all(after == was for was, after in with_calls[5]), "a LazyExtrinsics was left evaluated"
+    mid = lambda ns: ns.model.consistency(ns.out, offsets=(-2, -1, 1, 2), frames=(1, 3), details=True, tolerance=0.05)  # noqa: E731
+    after = lambda ns: ns.model.consistency(ns.out)  # noqa: E731
+    plain = train(dev, tracking=tracking, fuse=fuse, steps=steps, first_step=1, warm_up=True)
+    with_calls = train(dev, tracking=tracking, fuse=fuse, steps=steps, first_step=1, warm_up=True, calls=(mid, after))
+    assert_training_untouched(plain, with_calls, "depth_consistency", 2 * steps)
     if not tracking:
-        assert all(was for was, _ in with_calls[5]), "a flow-only training step hands out a LazyExtrinsics: the case must exercise it"
-    for r in with_calls[4]:
+        assert all(was for was, _ in with_calls.lazy_kept), "a flow-only training step hands out a LazyExtrinsics: the case must exercise it"
+    for r in with_calls.seen:
         assert bool(torch.isfinite(r.error).all()) and bool((r.code <= 3).all())
-    first, second = with_calls[4][0], with_calls[4][1]
+    first, second = with_calls.seen[0], with_calls.seen[1]
     assert first.error.shape == (1, 3, 4, 24, 32) and first.first_frame == 1 and second.error.shape == (1, 5, 2, 24, 32) and second.positions is None
 
 

@@ -13,7 +13,6 @@ What is compared, and how hard:
 
 import ctypes
 import re
-from contextlib import contextmanager
 from pathlib import Path
 
 import numpy as np
@@ -21,7 +20,7 @@ import torch
 
 import cases
 from conftest import assert_close
-from flowmap_amd import _ops
+from flowmap_amd import _ops, config
 from flowmap_amd._base import FLOW_BITMASK_CHUNK_BYTES
 from flowmap_amd._lib import call, ptr, stream_for
 from oracle import flowmap_oracle as orc
@@ -37,15 +36,9 @@ class FmFlowTaps(ctypes.Structure):
                 ("depth", ctypes.c_void_p), ("stale", ctypes.c_void_p)]
 
 
-@contextmanager
 def forced(bitmask: bool, first_sight: bool = True):
     """The Options switch that forces the fp32 format (False) or leaves the choice to the classification (True)."""
-    before = (_ops.options.packed_bitmask, _ops.options.pack_on_first_sight)
-    _ops.options.packed_bitmask, _ops.options.pack_on_first_sight = bitmask, first_sight
-    try:
-        yield
-    finally:
-        _ops.options.packed_bitmask, _ops.options.pack_on_first_sight = before
+    return config.override(packed_bitmask=bitmask, pack_on_first_sight=first_sight)
 
 
 def binary_flows(batch, f, h, w, seed=0, full=None):

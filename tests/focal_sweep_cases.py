@@ -26,7 +26,7 @@ import functools
 import torch
 
 from conftest import assert_close_or_reference_gap, load_golden, relerr, t
-from flow_residual_cases import ulp_distance
+from operator_checks import HEIGHT, WIDTH, assert_training_untouched, gate_pair, host_tensor_refused, same_tensors, train, ulp_distance, window_rows
 from oracle import flowmap_oracle as orc
 
 THREADS = 256  # threads per workgroup (fm_focal_sweep.hip: kSweepThreads)
@@ -83,14 +83,6 @@ def windows_of(frames):
     if pairs == 1:
         return [None]
     return [None, (0, 1), (pairs - 1, 1), slice(1, max(2, pairs - 1))]
-
-
-def window_rows(window, pairs):
-    if window is None:
-        return slice(0, pairs)
-    if isinstance(window, slice):
-        return slice(*window.indices(pairs)[:2])
-    return slice(window[0], window[0] + window[1])
 
 
 # ---- the oracle's per-pair sweep ----------------------------------------------------------------------------------------------------------
@@ -168,13 +160,6 @@ def check_fields(r, truth, ref32, what, rows=slice(None)):
     return worst
 
 
-def gate_pair(a, b, gap, what):
-    """Two fp32 evaluations of one quantity against each other: the same bound, max(1e-4, 2 x the fp32-to-fp64 gap of that quantity)."""
-    e = relerr(a, b)
-    assert e <= max(1e-4, 2.0 * gap), f"{what}: rel err {e:.3e} > max(1e-4, 2 x fp32-reference gap {gap:.3e})"
-    return e
-
-
 # ---- plumbing -----------------------------------------------------------------------------------------------------------------------------
 
 
@@ -201,13 +186,8 @@ def run(name, dev, **kw):
     return module.residuals(batch, flows, out, indices=None if idx is None else idx.to(dev), **kw)
 
 
-def same_fields(a, b, what="", rows=None):
-    for name in FIELDS + ("point_error",):
-        x, y = getattr(a, name), getattr(b, name)
-        assert (x is None) == (y is None), f"{what}{name}"
-        if x is not None:
-            y = y if rows is None else y[:, rows]
-            assert torch.equal(x, y), f"{what}{name}: not bit-equal (max |diff| {float((x.double() - y.double()).abs().max()):.3e})"
+def same_fields(a, b, what="", **kw):
+    same_tensors(a, b, FIELDS + ("point_error",), what, **kw)
 
 
 def check_layout(r, name, dev, count=None, first=0):
@@ -397,75 +377,35 @@ def _rng_state(dev):
 
 
 def _train(dev, tracking, fuse, regressed, calls, steps=3):
-    """One discarded forward + backward, then ``steps`` optimisation steps (flow loss, with ``tracking`` the tracking loss) with FusedAdam
-    (``fuse``: the depth update inside the flow pass) on a model with softmin intrinsics — ``regressed``: past the hand-over, else inside the
-    sweep's window; ``calls``: IntrinsicsSoftmin.residuals between forward and backward (a window, given indices) and between the steps
-    (every pair, indices=None).
+    """operator_checks.train, 3 steps from step 1 after the warm-up, on a model with softmin intrinsics — ``regressed``: past the hand-over,
+    else inside the sweep's window; ``calls``: IntrinsicsSoftmin.residuals between forward and backward (a window, given indices) and
+    between the steps (every pair, indices=None).  -> (the record, per call whether torch's generators and the seed state stayed put).
 
     The sweep draws 64 points for 6 candidates: the backward kernels of the sweep (fm_softmin_score_bwd, the fit's batch_repeat scatter) add
     into dL/ddepth with float atomics, one thread per point for a group of six candidates — at this size ONE wavefront issues all of them,
     so two runs add in the same order and the baseline itself is bit-reproducible on the GPU; with more points or candidates it is not, calls
     or no calls (cases.py, the fused-Adam trajectory: "float atomics whose order differs from run to run"), and nothing could be decided."""
-    import cases
-    import flowmap_amd
-    from flowmap_amd import FusedAdam, _ops
-    from flowmap_amd.loss import LossFlow, LossFlowCfg, LossTracking, LossTrackingCfg
     from flowmap_amd.model.intrinsics_softmin import IntrinsicsSoftminCfg, RegressionCfg
-    from helpers import mapping_cfg, to_tracks
 
-    min_bytes = _ops.options.tap_exchange_min_bytes
-    _ops.options.tap_exchange_min_bytes = 0
-    try:
-        torch.manual_seed(7)  # the sweep's own indices come from torch's CPU generator
-        f, h, w = 5, 24, 32
-        regression = RegressionCfg(1, 1) if regressed else RegressionCfg(100, 100)
-        model, batch, flows, _ = cases._small_problem(dev, f=f, h=h, w=w, tracking=False, intrinsics=IntrinsicsSoftminCfg("softmin", 64, 0.5, 2.0, 6, regression))
-        sc = orc.synth_scene(f, h, w, seed=21)
-        tracks = to_tracks(orc.synth_tracks(f, h, w, scene=sc, seed=21, interval=2, radius=2, grid=5), dev) if tracking else None
-        flow_fn = LossFlow(LossFlowCfg(0, 1000.0, "flow", mapping_cfg("huber")))
-        track_fn = LossTracking(LossTrackingCfg(0, 100.0, "tracking", mapping_cfg("huber")))
-        optimizer = FusedAdam(model.parameters(), lr=1e-3)
-        if fuse:
-            optimizer.fuse_depth_update(model.backbone.depth, max_touched_fraction=1.0)
-        model.train()
-        given = torch.randperm(h * w, generator=torch.Generator().manual_seed(9))[:100].to(dev)
+    given = torch.randperm(HEIGHT * WIDTH, generator=torch.Generator().manual_seed(9))[:100].to(dev)
+    rng_kept = []
 
-        def forward_loss(step):
-            out = model(batch, flows, step)
-            total = flow_fn(batch, flows, tracks, out, step)
-            return out, (total + track_fn(batch, flows, tracks, out, step) if tracking else total)
+    def probed(call):
+        def probe(ns):
+            state = _rng_state(dev)
+            r = call(ns)
+            rng_kept.append(_states_equal(state, _rng_state(dev)))
+            return r
 
-        # discarded: until the sparse fit's scatter plan exists its first backward adds into dL/ddepth with float atomics (DESIGN.md §4)
-        out, total = forward_loss(0)
-        total.backward()
-        optimizer.zero_grad(set_to_none=True)
-        del out, total
-        before = dict(_ops.counters)
-        history, seen, rng_kept = [], [], []
-        for step in range(1, steps + 1):
-            optimizer.zero_grad(set_to_none=True)
-            out, total = forward_loss(step)
-            if calls:
-                state = _rng_state(dev)
-                seen.append(model.intrinsics.residuals(batch, flows, out, pairs=(1, 2), indices=given, points=True))
-                rng_kept.append(_states_equal(state, _rng_state(dev)))
-            total.backward()
-            depth_grad = model.backbone.depth.grad
-            history.append([total.detach().clone(), None if (fuse or depth_grad is None) else depth_grad.detach().clone(), model.backbone.weights.grad.detach().clone()])
-            optimizer.step()
-            if calls:
-                state = _rng_state(dev)
-                seen.append(model.intrinsics.residuals(batch, flows, out, seed=step))
-                rng_kept.append(_states_equal(state, _rng_state(dev)))
-        moved = {key: value - before.get(key, 0) for key, value in _ops.counters.items()}
-        params = [p.detach().clone() for p in model.parameters()]
-        notes = sorted(key.rstrip("0123456789") for tensor in (flows.backward, model.backbone.depth, model.backbone.weights) for key in tensor.__dict__
-                       if key.startswith("_fm_"))
-        window = [v.detach().clone() for v in model.intrinsics.window]
-        return history, params, moved, notes, window, seen, rng_kept
-    finally:
-        _ops.options.tap_exchange_min_bytes = min_bytes
-        flowmap_amd.set_lazy_surfaces(False)
+        return probe
+
+    mid = probed(lambda ns: ns.model.intrinsics.residuals(ns.batch, ns.flows, ns.out, pairs=(1, 2), indices=given, points=True))
+    after = probed(lambda ns: ns.model.intrinsics.residuals(ns.batch, ns.flows, ns.out, seed=ns.step))
+    regression = RegressionCfg(1, 1) if regressed else RegressionCfg(100, 100)
+    run = train(dev, tracking=tracking, fuse=fuse, steps=steps, first_step=1, warm_up=True, calls=(mid, after) if calls else None,
+                intrinsics=IntrinsicsSoftminCfg("softmin", 64, 0.5, 2.0, 6, regression),
+                prepare=lambda ns: torch.manual_seed(7))  # the sweep's own indices come from torch's CPU generator
+    return run, rng_kept
 
 
 def _states_equal(a, b):
@@ -474,31 +414,20 @@ def _states_equal(a, b):
 
 
 def case_training_untouched(dev, tracking, fuse, regressed):
-    """Two identical runs of three steps, with and without residuals() calls (one of them with indices=None): the loss and the gradients
-    of every step and every parameter after the last are bit-equal, the module's window has the same length and entries, the operator
-    counters differ by ``focal_sweep`` alone, the same ``_fm_*`` notes sit on the flow, depth and weight tensors, and torch's CPU and
-    device generators and the graph-capturable seed state are unchanged across every call.  (With the depth update inside the flow pass
-    ``depth.grad`` is defined at the sparse pixels of the other operators only — there dL/ddepth is compared through the depth parameter it
-    moved, and element for element in the run with the separate update.)"""
+    """Two identical runs of three steps, with and without residuals() calls (one of them with indices=None):
+    operator_checks.assert_training_untouched with ``focal_sweep`` the one counter that differs, the module's window has the same length
+    and entries, and torch's CPU and device generators and the graph-capturable seed state are unchanged across every call."""
     steps = 3
-    plain = _train(dev, tracking, fuse, regressed, calls=False, steps=steps)
-    with_calls = _train(dev, tracking, fuse, regressed, calls=True, steps=steps)
-    for step, (a, b) in enumerate(zip(with_calls[0], plain[0])):
-        for x, y, what in zip(a, b, ("loss", "g_depth", "g_weights")):
-            assert (x is None) == (y is None)
-            if x is not None:
-                assert torch.equal(x, y), f"step {step}: {what} differs (max |diff| {float((x.double() - y.double()).abs().max()):.3e})"
-    assert len(with_calls[1]) == len(plain[1]) and all(torch.equal(x, y) for x, y in zip(with_calls[1], plain[1])), "the parameters after the last step differ"
-    moved, base = with_calls[2], plain[2]
-    assert moved.pop("focal_sweep") == 2 * steps and base.pop("focal_sweep") == 0
-    assert moved == base, (moved, base)
-    assert with_calls[3] == plain[3], (with_calls[3], plain[3])
-    assert len(with_calls[4]) == len(plain[4]) and all(torch.equal(x, y) for x, y in zip(with_calls[4], plain[4])), "the window differs"
-    assert len(plain[4]) == (1 if regressed else steps + 1)  # (the discarded step is a training step of the sweep too)
-    assert with_calls[6] and all(with_calls[6]), "a generator or the seed state moved across a call"
-    for r in with_calls[5]:
+    plain, _ = _train(dev, tracking, fuse, regressed, calls=False, steps=steps)
+    with_calls, rng_kept = _train(dev, tracking, fuse, regressed, calls=True, steps=steps)
+    assert_training_untouched(plain, with_calls, "focal_sweep", 2 * steps)
+    window, base_window = with_calls.model.intrinsics.window, plain.model.intrinsics.window
+    assert len(window) == len(base_window) and all(torch.equal(x, y) for x, y in zip(window, base_window)), "the window differs"
+    assert len(base_window) == (1 if regressed else steps + 1)  # (the discarded step is a training step of the sweep too)
+    assert len(rng_kept) == 2 * steps and all(rng_kept), "a generator or the seed state moved across a call"
+    for r in with_calls.seen:
         assert bool(torch.isfinite(r.error).all()) and bool(torch.isfinite(r.intrinsics).all())
-    first, second = with_calls[5][0], with_calls[5][1]
+    first, second = with_calls.seen[0], with_calls.seen[1]
     assert (first.first_pair, first.count) == (1, 2) and first.point_error.shape == (1, 2, 6, 100) and second.error.shape == (1, 4, 6) and second.indices.numel() == 64
 
 
@@ -612,15 +541,10 @@ def case_state_untouched(dev):
 
 
 def case_host_tensor_refused():
-    """Without the test double, host tensors are refused by name — through the method and through the function."""
-    import pytest
-
-    from flowmap_amd import _lib
+    """Host tensors are refused by name — through the method and through the function."""
     from flowmap_amd.model import projection as fm
 
-    _lib.set_library_for_testing(None)
     module, batch, flows, out = problem("tiny3", "cpu")
-    with pytest.raises(RuntimeError, match="flowmap_amd: focal_sweep: tensors are on cpu.*no CPU fallback"):
-        module.residuals(batch, flows, out)
-    with pytest.raises(RuntimeError, match="flowmap_amd: focal_sweep: tensors are on cpu"):
-        fm.focal_sweep(out.depths, out.weights, flows.backward, module.focal_length_candidates)
+    host_tensor_refused(lambda: module.residuals(batch, flows, out), "flowmap_amd: focal_sweep: tensors are on cpu.*no CPU fallback")
+    host_tensor_refused(lambda: fm.focal_sweep(out.depths, out.weights, flows.backward, module.focal_length_candidates),
+                        "flowmap_amd: focal_sweep: tensors are on cpu")

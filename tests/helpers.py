@@ -53,47 +53,45 @@ def run_ours(depth, wlogit, focal, oflows, hw, num_points, otracks=None, kind="h
     drive it.  Returns dict of loss values and parameter gradients (on CPU).  ``steps`` > 1: the same step repeated on the
     same parameters (no optimiser), the LAST one reported — from its second step on a flow + tracking loop runs the tap
     exchange, from its third the tracking loss samples the compact tap image (flowmap_amd/_ops.py: TapPlan)."""
-    from flowmap_amd import _ops
+    from flowmap_amd import config
 
     f = depth.shape[0]
     flowmap_amd.set_lazy_surfaces(lazy)
-    min_bytes = _ops.options.tap_exchange_min_bytes
-    try:
-        cfg = ModelCfg(
-            BackboneExplicitDepthCfg("explicit_depth", 1.0, 100.0),
-            IntrinsicsRegressedCfg("regressed", float(focal)),
-            ExtrinsicsProcrustesCfg("procrustes", num_points, False),
-        )
-        model = Model(cfg, num_frames=f, image_shape=tuple(hw))
-        model.backbone.depth.data = depth.clone()
-        model.backbone.weights.data = wlogit.clone()
-        model = model.to(device)
-        batch = Batch(torch.zeros((1, f, 3, *hw), device=device))
-        flows = to_flows(oflows, device)
-        tracks = to_tracks(otracks, device)
-        losses = [LossFlow(LossFlowCfg(0, flow_weight, "flow", mapping_cfg(kind)))]
-        if tracks is not None:
-            losses.append(LossTracking(LossTrackingCfg(0, track_weight, "tracking", mapping_cfg(kind))))
-        if steps > 1:
-            _ops.options.tap_exchange_min_bytes = 0  # (a repeated step is asked for to exercise the tap exchange, whatever the size)
-        for _ in range(steps):
-            model.zero_grad(set_to_none=True)
-            out = model(batch, flows, 0)
-            parts = [fn(batch, flows, tracks, out, 0) for fn in losses]
-            total = sum(parts) * loss_scale if loss_scale != 1.0 else sum(parts)
-            total.backward()
-        return {
-            "total": total.detach().cpu(),
-            "loss_flow": parts[0].detach().cpu(),
-            "loss_tracking": parts[1].detach().cpu() if tracks is not None else torch.zeros(()),
-            "extrinsics": out.extrinsics.detach().cpu(),
-            "g_depth": model.backbone.depth.grad.cpu(),
-            "g_wlogit": model.backbone.weights.grad.cpu(),
-            "g_focal": model.intrinsics.focal_length.grad.cpu(),
-        }
-    finally:
-        flowmap_amd.set_lazy_surfaces(False)
-        _ops.options.tap_exchange_min_bytes = min_bytes
+    # (a repeated step is asked for to exercise the tap exchange, whatever the size)
+    with config.override(**({"tap_exchange_min_bytes": 0} if steps > 1 else {})):
+        try:
+            cfg = ModelCfg(
+                BackboneExplicitDepthCfg("explicit_depth", 1.0, 100.0),
+                IntrinsicsRegressedCfg("regressed", float(focal)),
+                ExtrinsicsProcrustesCfg("procrustes", num_points, False),
+            )
+            model = Model(cfg, num_frames=f, image_shape=tuple(hw))
+            model.backbone.depth.data = depth.clone()
+            model.backbone.weights.data = wlogit.clone()
+            model = model.to(device)
+            batch = Batch(torch.zeros((1, f, 3, *hw), device=device))
+            flows = to_flows(oflows, device)
+            tracks = to_tracks(otracks, device)
+            losses = [LossFlow(LossFlowCfg(0, flow_weight, "flow", mapping_cfg(kind)))]
+            if tracks is not None:
+                losses.append(LossTracking(LossTrackingCfg(0, track_weight, "tracking", mapping_cfg(kind))))
+            for _ in range(steps):
+                model.zero_grad(set_to_none=True)
+                out = model(batch, flows, 0)
+                parts = [fn(batch, flows, tracks, out, 0) for fn in losses]
+                total = sum(parts) * loss_scale if loss_scale != 1.0 else sum(parts)
+                total.backward()
+            return {
+                "total": total.detach().cpu(),
+                "loss_flow": parts[0].detach().cpu(),
+                "loss_tracking": parts[1].detach().cpu() if tracks is not None else torch.zeros(()),
+                "extrinsics": out.extrinsics.detach().cpu(),
+                "g_depth": model.backbone.depth.grad.cpu(),
+                "g_wlogit": model.backbone.weights.grad.cpu(),
+                "g_focal": model.intrinsics.focal_length.grad.cpu(),
+            }
+        finally:
+            flowmap_amd.set_lazy_surfaces(False)
 
 
 def run_oracle(depth, wlogit, focal, oflows, hw, num_points, otracks=None, kind="huber", dtype=torch.float32,

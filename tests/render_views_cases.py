@@ -29,7 +29,7 @@ import math
 import torch
 
 from conftest import assert_close_or_reference_gap, load_golden, relerr, t
-from flow_residual_cases import ulp_distance
+from operator_checks import FRAMES, HEIGHT, WIDTH, assert_training_untouched, batch_colours, c_entry_refuses, host_tensor_refused, same_tensors, train, ulp_distance
 from oracle import flowmap_oracle as orc
 
 T = 1024  # source pixels per workgroup (fm_residual_args.h: kRenderTile)
@@ -280,14 +280,8 @@ def run(name, dev, x=None, colors=True, **changed):
     return flowmap_amd.render_views(y["depth"], y["k"], y["ext"], y["colors"] if colors else None, **kw)
 
 
-def same_render(a, b, what="", rows=None, batch=None):
-    for key in ("color", "depth", "source"):
-        p, q = getattr(a, key), getattr(b, key)
-        assert (p is None) == (q is None), f"{what}{key}"
-        if p is not None:
-            q = q if rows is None else q[:, rows]
-            q = q if batch is None else q[batch]
-            assert p.shape == q.shape and torch.equal(p, q), f"{what}{key}: not bit-equal"
+def same_render(a, b, what="", **kw):
+    same_tensors(a, b, ("color", "depth", "source"), what, **kw)
 
 
 def keys_of(r):
@@ -551,20 +545,7 @@ def case_c_entries_refuse(lib, what):
 
     from flowmap_amd import _lib
 
-    fn = lib.fm_render_views
-    fn.argtypes, fn.restype = _lib.SIGNATURES["fm_render_views"], ctypes.c_int
-    raw = ctypes.create_string_buffer(4096 + 64)  # what the non-null pointers point at: host memory, never dereferenced
-    address = (ctypes.addressof(raw) + 63) & ~63
-    for change in C_REFUSED:
-        nulls = change == "nulls"
-        change = {} if nulls else change
-        args = []
-        for param, kind in zip(C_PARAMS, _lib.SIGNATURES["fm_render_views"], strict=True):
-            if kind is ctypes.c_void_p:
-                args.append(None if nulls or param == "stream" or (param in change and change[param] is None) else address)
-            else:
-                args.append({**C_VALID, **change}[param])
-        assert fn(*args) == 1, f"{what}: fm_render_views did not refuse ({'all pointers null' if nulls else change})"
+    c_entry_refuses(lib, what, "fm_render_views", C_PARAMS, C_VALID, C_REFUSED)
     size = lib.fm_render_views_workspace
     size.argtypes, size.restype = _lib.SIGNATURES["fm_render_views_workspace"], ctypes.c_int
     out = ctypes.c_long(-1)
@@ -578,101 +559,27 @@ def case_c_entries_refuse(lib, what):
 
 
 def case_host_tensor_refused():
-    """Without the test double and without install(), host tensors are refused by name."""
-    import pytest
-
-    from flowmap_amd import _lib
-
-    _lib.set_library_for_testing(None)
-    with pytest.raises(RuntimeError, match="flowmap_amd: render_views: tensors are on cpu.*no CPU fallback"):
-        run("tiny", "cpu")
+    host_tensor_refused(lambda: run("tiny", "cpu"), "flowmap_amd: render_views: tensors are on cpu.*no CPU fallback")
 
 
 # ---- check 5: training is left alone -----------------------------------------------------------------------------------------------------------
 
 
-def _train(dev, tracking, fuse, calls, steps=3):
-    """One discarded forward + backward, then ``steps`` optimisation steps (flow loss, with ``tracking`` the tracking loss) with FusedAdam —
-    ``fuse``: the depth update inside the flow pass; ``calls``: Model.render between forward and backward (held-out, coloured from the
-    batch) and between the steps (free cameras)."""
-    import cases
-    import flowmap_amd
-    from flowmap_amd import FusedAdam, _ops
-    from flowmap_amd.loss import LossFlow, LossFlowCfg, LossTracking, LossTrackingCfg
-    from flowmap_amd.model.projection import LazyExtrinsics
-    from helpers import mapping_cfg, to_tracks
-
-    min_bytes = _ops.options.tap_exchange_min_bytes
-    _ops.options.tap_exchange_min_bytes = 0
-    try:
-        f, h, w = 5, 24, 32
-        model, batch, flows, _ = cases._small_problem(dev, f=f, h=h, w=w, tracking=False)
-        batch.videos = torch.rand((1, f, 3, h, w), generator=torch.Generator().manual_seed(5)).to(dev)
-        sc = orc.synth_scene(f, h, w, seed=21)
-        tracks = to_tracks(orc.synth_tracks(f, h, w, scene=sc, seed=21, interval=2, radius=2, grid=5), dev) if tracking else None
-        cams = (sc["intrinsics_gt"].expand(1, 2, 3, 3).contiguous().to(dev), sc["extrinsics_gt"][None, 1:3].contiguous().to(dev))
-        flow_fn = LossFlow(LossFlowCfg(0, 1000.0, "flow", mapping_cfg("huber")))
-        track_fn = LossTracking(LossTrackingCfg(0, 100.0, "tracking", mapping_cfg("huber")))
-        optimizer = FusedAdam(model.parameters(), lr=1e-3)
-        if fuse:
-            optimizer.fuse_depth_update(model.backbone.depth, max_touched_fraction=1.0)
-        model.train()
-
-        def forward_loss(step):
-            out = model(batch, flows, step)
-            total = flow_fn(batch, flows, tracks, out, step)
-            return out, (total + track_fn(batch, flows, tracks, out, step) if tracking else total)
-
-        out, total = forward_loss(0)
-        total.backward()
-        optimizer.zero_grad(set_to_none=True)
-        del out, total
-        before = dict(_ops.counters)
-        history, seen, lazy_kept = [], [], []
-        for step in range(1, steps + 1):
-            optimizer.zero_grad(set_to_none=True)
-            out, total = forward_loss(step)
-            if calls:
-                was_lazy = isinstance(out.extrinsics, LazyExtrinsics) and out.extrinsics._dense is None
-                seen.append(model.render(out, batch, held_out=(1, 3), radius=1))
-                lazy_kept.append((was_lazy, isinstance(out.extrinsics, LazyExtrinsics) and out.extrinsics._dense is None))
-            total.backward()
-            depth_grad = model.backbone.depth.grad
-            history.append([total.detach().clone(), None if (fuse or depth_grad is None) else depth_grad.detach().clone(), model.backbone.weights.grad.detach().clone()])
-            optimizer.step()
-            if calls:
-                seen.append(model.render(out, views=cams, shape=(12, 16)))
-        moved = {key: value - before.get(key, 0) for key, value in _ops.counters.items()}
-        params = [p.detach().clone() for p in model.parameters()]
-        notes = sorted(key.rstrip("0123456789") for tensor in (flows.backward, model.backbone.depth, model.backbone.weights) for key in tensor.__dict__
-                       if key.startswith("_fm_"))
-        return history, params, moved, notes, seen, lazy_kept
-    finally:
-        _ops.options.tap_exchange_min_bytes = min_bytes
-        flowmap_amd.set_lazy_surfaces(False)
-
-
 def case_training_untouched(dev, tracking, fuse):
-    """Two identical runs of three steps, with and without render() calls: the loss and the gradients of every step and every parameter after
-    the last are bit-equal, the operator counters differ by ``render_views`` alone, the same ``_fm_*`` notes sit on the flow, depth and
-    weight tensors, and a LazyExtrinsics handed in is still unevaluated afterwards."""
+    """operator_checks.train, 3 steps from step 1 after the warm-up, with and without Model.render between forward and backward (held-out,
+    coloured from the batch) and between the steps (free cameras): operator_checks.assert_training_untouched with ``render_views`` the
+    one counter that differs — a LazyExtrinsics handed in is still unevaluated afterwards, and a flow-only step does hand one in."""
     steps = 3
-    plain = _train(dev, tracking, fuse, calls=False, steps=steps)
-    with_calls = _train(dev, tracking, fuse, calls=True, steps=steps)
-    for step, (a, b) in enumerate(zip(with_calls[0], plain[0])):
-        for x, y, what in zip(a, b, ("loss", "g_depth", "g_weights")):
-            assert (x is None) == (y is None)
-            if x is not None:
-                assert torch.equal(x, y), f"step {step}: {what} differs (max |diff| {float((x.double() - y.double()).abs().max()):.3e})"
-    assert len(with_calls[1]) == len(plain[1]) and all(torch.equal(x, y) for x, y in zip(with_calls[1], plain[1])), "the parameters after the last step differ"
-    moved, base = with_calls[2], plain[2]
-    assert moved.pop("render_views") == 2 * steps and base.pop("render_views") == 0
-    assert moved == base, (moved, base)
-    assert with_calls[3] == plain[3], (with_calls[3], plain[3])
-    assert all(after == was for was, after in with_calls[5]), "a LazyExtrinsics was left evaluated"
+    sc = orc.synth_scene(FRAMES, HEIGHT, WIDTH, seed=21)  # (the training problem's scene: two of its true cameras)
+    cams = (sc["intrinsics_gt"].expand(1, 2, 3, 3).contiguous().to(dev), sc["extrinsics_gt"][None, 1:3].contiguous().to(dev))
+    mid = lambda ns: ns.model.render(ns.out, ns.batch, held_out=(1, 3), radius=1)  # noqa: E731
+    after = lambda ns: ns.model.render(ns.out, views=cams, shape=(12, 16))  # noqa: E731
+    plain = train(dev, tracking=tracking, fuse=fuse, steps=steps, first_step=1, warm_up=True, prepare=batch_colours)
+    with_calls = train(dev, tracking=tracking, fuse=fuse, steps=steps, first_step=1, warm_up=True, prepare=batch_colours, calls=(mid, after))
+    assert_training_untouched(plain, with_calls, "render_views", 2 * steps)
     if not tracking:
-        assert all(was for was, _ in with_calls[5]), "a flow-only training step hands out a LazyExtrinsics: the case must exercise it"
-    first, second = with_calls[4][0], with_calls[4][1]
+        assert all(was for was, _ in with_calls.lazy_kept), "a flow-only training step hands out a LazyExtrinsics: the case must exercise it"
+    first, second = with_calls.seen[0], with_calls.seen[1]
     assert first.color.shape == (1, 3, 3, 24, 32) and first.first_frame == 1 and first.offsets == PM2 and float(first.coverage().min()) > 0.5
     assert second.color is None and second.source.shape == (1, 2, 12, 16) and second.first_frame is None
 

@@ -298,7 +298,7 @@ def test_c4_whole_1200x1080x1920_on_one_gpu():
         fp64 oracle): Σ loss_s·V_s = loss·V, interior frames' dL/ddepth equal, halo frames' sum, Σ dL/dfocal_s·V_s = dL/dfocal·V;
       * a four-frame window BEYOND element 2^31 (frames 1100..1103) against the fp64 oracle: dL/ddepth and dL/dweights of its interior
         frames / pair depend on nothing outside the window (the relative pose of a pair is a function of its two frames)."""
-    from flowmap_amd import Flows, _ops
+    from flowmap_amd import Flows, config
     from flowmap_amd.sharding import shard_frames, shard_pairs
     from helpers import run_oracle
 
@@ -312,8 +312,7 @@ def test_c4_whole_1200x1080x1920_on_one_gpu():
                   torch.rand((1, f - 1, h, w), device=DEV, generator=g), torch.rand((1, f - 1, h, w), device=DEV, generator=g))
     assert depth.numel() > 2**31 and flows.forward.numel() > 2**32
 
-    _ops.options.pack_on_first_sight = True
-    try:
+    with config.override(pack_on_first_sight=True):
         whole = _gpu_step(depth, wlogit, flows, (h, w), p)
         assert flows.forward.__dict__.get("_fm_packed") is not None, "the whole-video step did not run the packed kernel"
         assert flows.forward.__dict__["_fm_packed"][1][1].numel() > 2**32
@@ -371,5 +370,3 @@ def test_c4_whole_1200x1080x1920_on_one_gpu():
         assert record["shard_g_depth_interior"] <= 1e-4 and record["shard_g_depth_halo"] <= 1e-4 and record["shard_g_wlogit"] <= 1e-4, record
         for key in ("g_depth", "g_depth[procrustes]", "g_wlogit"):
             assert record["window_" + key] <= max(1e-4, 2.0 * record["window_" + key + "_fp32_reference_gap"]), (key, record)
-    finally:
-        _ops.options.pack_on_first_sight = False

@@ -214,13 +214,11 @@ def test_the_state_machine_around_the_graphs(standin):
         assert state.signature(wrapper) is None
         handle.remove()
         assert state.signature(wrapper) is not None
-        from flowmap_amd import _ops
+        from flowmap_amd import config
 
-        previous, _ops.options.tap_exchange_min_bytes = _ops.options.tap_exchange_min_bytes, wrapper.model.backbone.depth.numel() * 4
-        try:  # depth maps from the size at which the tap exchange engages: HBM-bound, the eager step stays
+        # depth maps from the size at which the tap exchange engages: HBM-bound, the eager step stays
+        with config.override(tap_exchange_min_bytes=wrapper.model.backbone.depth.numel() * 4):
             assert state.signature(wrapper) is None
-        finally:
-            _ops.options.tap_exchange_min_bytes = previous
         assert state.signature(wrapper) is not None
         assert isinstance(training.make_training_step(eager).__wrapped__, type(eager))
     finally:

@@ -22,6 +22,7 @@ import torch
 import track_geometry_cases as tg
 from conftest import assert_close, assert_close_or_reference_gap, load_golden, maxerr, relerr, t
 from helpers import mapping_cfg
+from operator_checks import assert_training_untouched, host_tensor_refused, same_tensors, train, ulp_distance
 from oracle import flowmap_oracle as orc
 from track_geometry_cases import DELTA, SPECS, TOL, Spec, check_conditions, device_tracks, make_case  # noqa: F401
 
@@ -179,13 +180,8 @@ def check_segment(r, truth, ref32, what, skip=None):
         print(f"[{what}] {name}: ours/fp64 {err:.3e}  fp32 reference/fp64 {gap:.3e}", flush=True)
 
 
-def same_fields(a, b, what=""):
-    assert a.segment == b.segment and a.start_frame == b.start_frame, what
-    for name in ("residual", "visible", "xy_target", "pair_sum", "pair_count", "track_sum", "track_count"):
-        x, y = getattr(a, name), getattr(b, name)
-        assert (x is None) == (y is None), f"{what}{name}"
-        if x is not None:
-            assert x.shape == y.shape and x.dtype == y.dtype and torch.equal(x, y), f"{what}{name}: not bit-equal"
+def same_fields(a, b, what="", **kw):
+    same_tensors(a, b, ("residual", "visible", "xy_target", "pair_sum", "pair_count", "track_sum", "track_count"), what, scalars=("segment", "start_frame"), **kw)
 
 
 # ---- 1: reference parity ------------------------------------------------------------------------------------------------------------------
@@ -383,95 +379,28 @@ def case_camera_plane(dev, kind):
 # ---- 6: training is left alone ----------------------------------------------------------------------------------------------------------------
 
 
-def _train(dev, calls, fuse, steps=5):
-    """``steps`` optimisation steps of flow + tracking with the tap exchange and FusedAdam (``fuse``: the depth update inside the flow pass);
-    ``calls``: LossTracking.residuals between forward and backward and again between the steps."""
-    import cases
-    import flowmap_amd
-    from flowmap_amd import FusedAdam, _ops
-    from flowmap_amd.loss import LossFlow, LossFlowCfg, LossTracking, LossTrackingCfg
-    from helpers import to_tracks
-
-    min_bytes = _ops.options.tap_exchange_min_bytes
-    _ops.options.tap_exchange_min_bytes = 0
-    try:
-        f, h, w = 5, 24, 32
-        model, batch, flows, _ = cases._small_problem(dev, f=f, h=h, w=w, tracking=False)
-        sc = orc.synth_scene(f, h, w, seed=21)
-        tracks = to_tracks(orc.synth_tracks(f, h, w, scene=sc, seed=21, interval=2, radius=2, grid=5), dev)
-        flow_fn = LossFlow(LossFlowCfg(0, 1000.0, "flow", mapping_cfg("huber")))
-        track_fn = LossTracking(LossTrackingCfg(0, 100.0, "tracking", mapping_cfg("huber")))
-        optimizer = FusedAdam(model.parameters(), lr=1e-3)
-        if fuse:
-            optimizer.fuse_depth_update(model.backbone.depth, max_touched_fraction=1.0)
-        focal = next(p for name, p in model.named_parameters() if name.endswith("focal_length"))
-        # One forward + backward whose gradients are thrown away, in both runs, before anything is compared: the sparse fit's scatter plan is
-        # built when the same (indices, flows) come back a second time, and until it exists fm_procrustes_scatter adds into dL/ddepth with
-        # float atomics — two runs of that FIRST backward differ in the last bit of dL/ddepth where two taps share a pixel (DESIGN.md §4,
-        # "Determinism"), calls or no calls, and Adam would carry the bit into every later step.  No parameter moves here.
-        out = model(batch, flows, 0)
-        (flow_fn(batch, flows, tracks, out, 0) + track_fn(batch, flows, tracks, out, 0)).backward()
-        optimizer.zero_grad(set_to_none=True)
-        del out
-        before = dict(_ops.counters)
-        history, seen = [], []
-        for step in range(steps):
-            optimizer.zero_grad(set_to_none=True)
-            out = model(batch, flows, step)
-            total = flow_fn(batch, flows, tracks, out, step) + track_fn(batch, flows, tracks, out, step)
-            if calls:
-                seen.append(track_fn.residuals(batch, tracks, out, segments=(1, 1), predicted=True))
-            total.backward()
-            history.append([total.detach().clone()] + [p.grad.detach().clone() for p in (model.backbone.depth, model.backbone.weights, focal)])
-            optimizer.step()
-            if calls:
-                seen.append(track_fn.residuals(batch, tracks, out))
-        moved = {key: value - before.get(key, 0) for key, value in _ops.counters.items()}
-        params = [p.detach().clone() for p in (model.backbone.depth, model.backbone.weights, focal)]
-        state = {"in_pass": optimizer.counters.get("in_pass_updates", 0), "depth_version": model.backbone.depth._version}
-        return history, params, moved, state, seen, len(tracks)
-    finally:
-        _ops.options.tap_exchange_min_bytes = min_bytes
-        flowmap_amd.set_lazy_surfaces(False)
-
-
 def case_training_untouched(dev, fuse):
-    """With and without residuals() between forward and backward and between the steps: the loss and every gradient of every step and the
-    parameters at the end are bit-equal, the operator counters differ by ``track_residuals`` alone, the tap exchange ran in both.  (With the
-    depth update inside the flow pass depth.grad is defined at sparse pixels only — flow_residual_cases.case_training_untouched — so there
-    dL/ddepth is compared through the depth parameter it moved.)"""
+    """operator_checks.train, flow + tracking, 5 steps from step 0 after the warm-up, with and without LossTracking.residuals between forward
+    and backward (one segment, with the predicted positions) and between the steps: operator_checks.assert_training_untouched with
+    ``track_residuals`` the one counter that differs, and the tap exchange ran in both."""
     steps = 5
-    plain = _train(dev, calls=False, fuse=fuse, steps=steps)
-    with_calls = _train(dev, calls=True, fuse=fuse, steps=steps)
-    for step, (a, b) in enumerate(zip(with_calls[0], plain[0])):
-        for x, y, what in zip(a, b, ("loss", "g_depth", "g_weights", "g_focal")):
-            if fuse and what == "g_depth":
-                continue
-            assert torch.equal(x, y), f"step {step}: {what} differs (max |diff| {float((x.double() - y.double()).abs().max()):.3e})"
-    for x, y, what in zip(with_calls[1], plain[1], ("depth", "weights", "focal")):
-        assert torch.equal(x, y), f"{what} after {steps} steps differs"
-    moved, base = dict(with_calls[2]), dict(plain[2])
-    assert moved.pop("track_residuals") == 2 * steps and base.pop("track_residuals") == 0
-    assert moved == base, (moved, base)
-    assert with_calls[3] == plain[3], (with_calls[3], plain[3])
-    assert plain[3]["in_pass"] >= (steps - 3 if fuse else 0)
+    mid = lambda ns: ns.track_fn.residuals(ns.batch, ns.tracks, ns.out, segments=(1, 1), predicted=True)  # noqa: E731
+    after = lambda ns: ns.track_fn.residuals(ns.batch, ns.tracks, ns.out)  # noqa: E731
+    plain = train(dev, tracking=True, fuse=fuse, steps=steps, first_step=0, warm_up=True)
+    with_calls = train(dev, tracking=True, fuse=fuse, steps=steps, first_step=0, warm_up=True, calls=(mid, after))
+    moved, base = assert_training_untouched(plain, with_calls, "track_residuals", 2 * steps)
+    assert plain.state["in_pass"] >= (steps - 3 if fuse else 0)
     assert base["procrustes_plans_built"] == 1 and base["procrustes_planned"] == steps  # (every compared backward went through the plan)
     assert base["flow_tap_passes"] > 0 and moved["flow_tap_passes"] > 0  # the tap exchange really ran, in both runs
-    segments = with_calls[5]
-    for i, rs in enumerate(with_calls[4]):
+    segments = with_calls.state["segments"]
+    for i, rs in enumerate(with_calls.seen):
         assert len(rs) == (1 if i % 2 == 0 else segments)
         for r in rs:
             assert bool(torch.isfinite(r.residual).all()) and bool(torch.isfinite(r.pair_sum).all())
-    assert with_calls[4][0][0].segment == 1 and with_calls[4][0][0].xy_target is not None
+    assert with_calls.seen[0][0].segment == 1 and with_calls.seen[0][0].xy_target is not None
 
 
 # ---- 7: the GPU against the host double -------------------------------------------------------------------------------------------------------
-
-
-def ulp_distance(a, b):
-    from flow_residual_cases import ulp_distance as distance
-
-    return distance(a, b)
 
 
 def _inputs_of(which):
@@ -575,18 +504,14 @@ def case_arguments(dev):
 
 
 def case_host_tensor_refused():
-    """Without install() and without the test double, host tensors are refused with the package's message (test_abi.py::test_no_cpu_fallback),
-    on the fused route and on the general one."""
-    import pytest
-
-    from flowmap_amd import _lib
-
-    _lib.set_library_for_testing(None)
+    """Host tensors are refused on the fused route and on the general one."""
     spec, leaves, tracks = golden_problem("a")
     for lazy in (True, False):
-        with pytest.raises(RuntimeError, match="no CPU fallback|needs a GPU"):
+        def call(lazy=lazy):
             loss, batch, trk, out = problem(leaves, tracks, spec.hw, "cpu", lazy=lazy)
             loss.residuals(batch, trk, out)
+
+        host_tensor_refused(call, "no CPU fallback|needs a GPU")
 
 
 # ---- 9: the negative control ----------------------------------------------------------------------------------------------------------------

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from conftest import load_golden, t
+from operator_checks import assert_training_untouched, batch_colours, c_entry_refuses, host_tensor_refused, same_tensors, train
 from oracle import flowmap_oracle as orc
 
 T = 1024  # pixels per workgroup (fm_residual_args.h: kVoxelTile)
@@ -311,12 +312,7 @@ def bits(a):
 
 def same_cloud(a, b, what):
     """Two VoxelClouds equal bit for bit in every field."""
-    assert a.dropped == b.dropped, f"{what}: dropped {a.dropped} vs {b.dropped}"
-    for field in ("xyz", "rgb", "count", "first", "voxel_of"):
-        u, v = getattr(a, field), getattr(b, field)
-        assert (u is None) == (v is None), f"{what}: {field}"
-        if u is not None:
-            assert u.shape == v.shape and u.dtype == v.dtype and np.array_equal(bits(u), bits(v)), f"{what}: {field} differs"
+    same_tensors(a, b, ("xyz", "rgb", "count", "first", "voxel_of"), f"{what}: ", scalars=("dropped",), equal=lambda u, v: np.array_equal(bits(u), bits(v)))
 
 
 # ---- checks 1 and 2 -----------------------------------------------------------------------------------------------------------------------
@@ -557,21 +553,8 @@ def case_c_entries_refuse(lib, what):
 
     from flowmap_amd import _lib
 
-    fn = lib.fm_voxel_cloud
-    fn.argtypes, fn.restype = _lib.SIGNATURES["fm_voxel_cloud"], ctypes.c_int
-    raw = ctypes.create_string_buffer(4096 + 64)  # what the non-null pointers point at: host memory, never dereferenced
-    address = (ctypes.addressof(raw) + 63) & ~63
-    for change in C_REFUSED:
-        nulls = change == "nulls"
-        change = {} if nulls else change
-        args = []
-        for param, kind in zip(C_PARAMS, _lib.SIGNATURES["fm_voxel_cloud"], strict=True):
-            if kind is ctypes.c_void_p:
-                null = nulls or param == "stream" or (param in change and change[param] is None)
-                args.append(None if null else address + (4 if change.get(param) == "misaligned" else 0))
-            else:
-                args.append({**C_VALID, **change}[param])
-        assert fn(*args) == 1, f"{what}: fm_voxel_cloud did not refuse ({'all pointers null' if nulls else change})"
+    c_entry_refuses(lib, what, "fm_voxel_cloud", C_PARAMS, C_VALID, C_REFUSED,
+                    pointer=lambda param, change, address: address + (4 if change.get(param) == "misaligned" else 0))
     size = lib.fm_voxel_cloud_workspace
     size.argtypes, size.restype = _lib.SIGNATURES["fm_voxel_cloud_workspace"], ctypes.c_int
     slots, nbytes = ctypes.c_long(-1), ctypes.c_long(-1)
@@ -585,16 +568,11 @@ def case_c_entries_refuse(lib, what):
 
 
 def case_host_tensor_refused():
-    """Without the test double, host tensors are refused by name: there is no reference function to hand over to."""
-    import pytest
-
+    """Host tensors are refused by name: there is no reference function to hand over to."""
     import flowmap_amd
-    from flowmap_amd import _lib
 
-    _lib.set_library_for_testing(None)
     x = case_inputs("tiny")
-    with pytest.raises(RuntimeError, match="flowmap_amd: tensors are on cpu.*no CPU fallback"):
-        flowmap_amd.voxel_point_cloud(x["depth"], x["k"], x["ext"], x["colors"], 0.25)
+    host_tensor_refused(lambda: flowmap_amd.voxel_point_cloud(x["depth"], x["k"], x["ext"], x["colors"], 0.25), "flowmap_amd: tensors are on cpu.*no CPU fallback")
 
 
 # ---- check 6: the other operators are left alone -------------------------------------------------------------------------------------------
@@ -615,86 +593,19 @@ def case_world_points_unchanged(dev):
     assert float((before[0].cpu() - t(z["points"])).abs().max()) < 1e-5 and torch.equal(before[1].cpu(), t(z["point_colors"]))
 
 
-def _train(dev, tracking, fuse, calls, steps=3):
-    """render_views_cases._train with Model.point_cloud in place of Model.render: between forward and backward (coloured from the batch,
-    with details) and between the steps."""
-    import cases
-    import flowmap_amd
-    from flowmap_amd import FusedAdam, _ops
-    from flowmap_amd.loss import LossFlow, LossFlowCfg, LossTracking, LossTrackingCfg
-    from flowmap_amd.model.projection import LazyExtrinsics
-    from helpers import mapping_cfg, to_tracks
-
-    min_bytes = _ops.options.tap_exchange_min_bytes
-    _ops.options.tap_exchange_min_bytes = 0
-    try:
-        f, h, w = 5, 24, 32
-        model, batch, flows, _ = cases._small_problem(dev, f=f, h=h, w=w, tracking=False)
-        batch.videos = torch.rand((1, f, 3, h, w), generator=torch.Generator().manual_seed(5)).to(dev)
-        sc = orc.synth_scene(f, h, w, seed=21)
-        tracks = to_tracks(orc.synth_tracks(f, h, w, scene=sc, seed=21, interval=2, radius=2, grid=5), dev) if tracking else None
-        flow_fn = LossFlow(LossFlowCfg(0, 1000.0, "flow", mapping_cfg("huber")))
-        track_fn = LossTracking(LossTrackingCfg(0, 100.0, "tracking", mapping_cfg("huber")))
-        optimizer = FusedAdam(model.parameters(), lr=1e-3)
-        if fuse:
-            optimizer.fuse_depth_update(model.backbone.depth, max_touched_fraction=1.0)
-        model.train()
-
-        def forward_loss(step):
-            out = model(batch, flows, step)
-            total = flow_fn(batch, flows, tracks, out, step)
-            return out, (total + track_fn(batch, flows, tracks, out, step) if tracking else total)
-
-        out, total = forward_loss(0)
-        total.backward()
-        optimizer.zero_grad(set_to_none=True)
-        del out, total
-        before = dict(_ops.counters)
-        history, seen, lazy_kept = [], [], []
-        for step in range(1, steps + 1):
-            optimizer.zero_grad(set_to_none=True)
-            out, total = forward_loss(step)
-            if calls:
-                was_lazy = isinstance(out.extrinsics, LazyExtrinsics) and out.extrinsics._dense is None
-                seen.append(model.point_cloud(out, batch, voxel_size=0.05, details=True))
-                lazy_kept.append((was_lazy, isinstance(out.extrinsics, LazyExtrinsics) and out.extrinsics._dense is None))
-            total.backward()
-            depth_grad = model.backbone.depth.grad
-            history.append([total.detach().clone(), None if (fuse or depth_grad is None) else depth_grad.detach().clone(), model.backbone.weights.grad.detach().clone()])
-            optimizer.step()
-            if calls:
-                seen.append(model.point_cloud(out, voxel_size=0.1, min_count=2))
-        moved = {key: value - before.get(key, 0) for key, value in _ops.counters.items()}
-        params = [p.detach().clone() for p in model.parameters()]
-        notes = sorted(key.rstrip("0123456789") for tensor in (flows.backward, model.backbone.depth, model.backbone.weights) for key in tensor.__dict__
-                       if key.startswith("_fm_"))
-        return history, params, moved, notes, seen, lazy_kept
-    finally:
-        _ops.options.tap_exchange_min_bytes = min_bytes
-        flowmap_amd.set_lazy_surfaces(False)
-
-
 def case_training_untouched(dev, tracking, fuse):
-    """Two identical runs of three steps, with and without point_cloud() calls: the loss and the gradients of every step and every
-    parameter after the last are bit-equal, the operator counters differ by ``voxel_cloud`` alone, the same ``_fm_*`` notes sit on the
-    flow, depth and weight tensors, and a LazyExtrinsics handed in is still unevaluated afterwards."""
+    """operator_checks.train, 3 steps from step 1 after the warm-up, with and without Model.point_cloud between forward and backward
+    (coloured from the batch, with details) and between the steps: operator_checks.assert_training_untouched with ``voxel_cloud`` the one
+    counter that differs — a LazyExtrinsics handed in is still unevaluated afterwards, and a flow-only step does hand one in."""
     steps = 3
-    plain = _train(dev, tracking, fuse, calls=False, steps=steps)
-    with_calls = _train(dev, tracking, fuse, calls=True, steps=steps)
-    for step, (a, b) in enumerate(zip(with_calls[0], plain[0])):
-        for u, v, what in zip(a, b, ("loss", "g_depth", "g_weights")):
-            assert (u is None) == (v is None)
-            if u is not None:
-                assert torch.equal(u, v), f"step {step}: {what} differs (max |diff| {float((u.double() - v.double()).abs().max()):.3e})"
-    assert len(with_calls[1]) == len(plain[1]) and all(torch.equal(u, v) for u, v in zip(with_calls[1], plain[1])), "the parameters after the last step differ"
-    moved, base = with_calls[2], plain[2]
-    assert moved.pop("voxel_cloud") == 2 * steps and base.pop("voxel_cloud") == 0
-    assert moved == base, (moved, base)
-    assert with_calls[3] == plain[3], (with_calls[3], plain[3])
-    assert all(after == was for was, after in with_calls[5]), "a LazyExtrinsics was left evaluated"
+    mid = lambda ns: ns.model.point_cloud(ns.out, ns.batch, voxel_size=0.05, details=True)  # noqa: E731
+    after = lambda ns: ns.model.point_cloud(ns.out, voxel_size=0.1, min_count=2)  # noqa: E731
+    plain = train(dev, tracking=tracking, fuse=fuse, steps=steps, first_step=1, warm_up=True, prepare=batch_colours)
+    with_calls = train(dev, tracking=tracking, fuse=fuse, steps=steps, first_step=1, warm_up=True, prepare=batch_colours, calls=(mid, after))
+    assert_training_untouched(plain, with_calls, "voxel_cloud", 2 * steps)
     if not tracking:
-        assert all(was for was, _ in with_calls[5]), "a flow-only training step hands out a LazyExtrinsics: the case must exercise it"
-    first, second = with_calls[4][0], with_calls[4][1]
+        assert all(was for was, _ in with_calls.lazy_kept), "a flow-only training step hands out a LazyExtrinsics: the case must exercise it"
+    first, second = with_calls.seen[0], with_calls.seen[1]
     assert first.rgb is not None and tuple(first.voxel_of.shape) == (5, 24, 32) and len(first) > 100
     assert second.rgb is None and second.voxel_of is None and int(second.count.min()) >= 2
 
