@@ -18,16 +18,16 @@ GPU tensors never reach it, and without ``install()`` there is nothing to hand o
 
 from . import config, flow, loss, model  # noqa: F401
 from .install import install, uninstall  # noqa: F401
-from .export import voxel_point_cloud  # noqa: F401
+from .export import tsdf_volume, voxel_point_cloud  # noqa: F401
 from .model.projection import depth_consistency, render_views, set_lazy_surfaces  # noqa: F401
 from .model.extrinsics_regressed import ExtrinsicsRegressed, ExtrinsicsRegressedCfg  # noqa: F401
 from .graph import GraphedShardedStep, GraphedStep  # noqa: F401
 from .host import freeze_gc  # noqa: F401
 from ._ops import release_flow_originals  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
-from .types import AlignmentResiduals, BackboneOutput, Batch, DepthConsistency, FlowResiduals, Flows, FocalSweep, ModelOutput, RenderedViews, TrackResiduals, Tracks, VoxelCloud  # noqa: F401
+from .types import AlignmentResiduals, BackboneOutput, Batch, DepthConsistency, FlowResiduals, Flows, FocalSweep, ModelOutput, RenderedViews, TrackResiduals, Tracks, TsdfVolume, VoxelCloud  # noqa: F401
 
 __all__ = [
-    "config", "loss", "model", "install", "uninstall", "set_lazy_surfaces", "depth_consistency", "render_views", "voxel_point_cloud", "FusedAdam", "GraphedStep", "GraphedShardedStep", "freeze_gc", "release_flow_originals",
-    "Batch", "BackboneOutput", "AlignmentResiduals", "DepthConsistency", "FlowResiduals", "FocalSweep", "RenderedViews", "TrackResiduals", "Flows", "ModelOutput", "Tracks", "VoxelCloud", "ExtrinsicsRegressed", "ExtrinsicsRegressedCfg",
+    "config", "loss", "model", "install", "uninstall", "set_lazy_surfaces", "depth_consistency", "render_views", "voxel_point_cloud", "tsdf_volume", "FusedAdam", "GraphedStep", "GraphedShardedStep", "freeze_gc", "release_flow_originals",
+    "Batch", "BackboneOutput", "AlignmentResiduals", "DepthConsistency", "FlowResiduals", "FocalSweep", "RenderedViews", "TrackResiduals", "Flows", "ModelOutput", "Tracks", "TsdfVolume", "VoxelCloud", "ExtrinsicsRegressed", "ExtrinsicsRegressedCfg",
 ]

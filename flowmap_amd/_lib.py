@@ -129,6 +129,10 @@ SIGNATURES = {
     "fm_render_views": [P] * 7 + [I] * 9 + [F, F] + [P] * 5,
     "fm_voxel_cloud_workspace": [L, P, P],
     "fm_voxel_cloud": [P] * 5 + [I, I, I, D, I, L] + [P] * 9,
+    "fm_tsdf_volume": [P] * 5 + [I] * 5 + [F] * 3 + [I] * 3 + [F] * 3 + [P] * 6,
+    "fm_tsdf_surface_blocks": [I, I, I, P],
+    "fm_tsdf_surface_count": [P, P, I, I, I, I, P, P],
+    "fm_tsdf_surface_emit": [P] * 4 + [I, I, I, F, F, F, F, I, P, L] + [P] * 5,
 }
 
 _lib: Optional[ctypes.CDLL] = None

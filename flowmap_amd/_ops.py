@@ -242,7 +242,7 @@ def _dense_flow_is_rough(bwd_flow: Tensor, h: int, w: int) -> bool:
 # which backward path the facades selected (tests)
 counters = {"procrustes_planned": 0, "procrustes_dense_planned": 0, "flow_packs": 0, "flow_packs_bitmask": 0, "procrustes_plans_built": 0, "track_tap_samples": 0,
             "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0, "flow_residuals": 0, "track_residuals": 0, "alignment_residuals": 0, "focal_sweep": 0,
-            "depth_consistency": 0, "render_views": 0, "voxel_cloud": 0}
+            "depth_consistency": 0, "render_views": 0, "voxel_cloud": 0, "tsdf_volume": 0}
 
 
 class LeadingFrames:
@@ -899,6 +899,24 @@ def voxel_cloud(depth, kinv, ext, colors, keep, voxel_size, min_count, capacity,
                                                                                bool(details))
     counters["voxel_cloud"] += 1
     return xyz, (rgb if colors is not None else None), count, first, slot, (pixel_slot if details else None), counts
+
+
+def tsdf_volume(depth, k, ext, colors, keep, first_frame, count, origin, dims, voxel_size, truncation, near):
+    """The depth maps of frames [first_frame, first_frame + count) averaged into a truncated-signed-distance grid (csrc/fm_torch.cpp:
+    tsdf_volume_op -> fm_tsdf_volume): (world_to_camera (F,4,4), tsdf (nz,ny,nx), weight, color (nz,ny,nx,3), color_weight) — the last two
+    None without ``colors``.  One thread per frame for the poses, one per voxel for the volume; no atomics, no workspace.  Reads its
+    arguments and nothing else."""
+    w2c, tsdf, weight, color, color_weight = torch_ops().tsdf_volume(depth, k, ext, colors, keep, int(first_frame), int(count), *(float(v) for v in origin),
+                                                                     *(int(v) for v in dims), float(voxel_size), float(truncation), float(near))
+    counters["tsdf_volume"] += 1
+    return w2c, tsdf, weight, (color if colors is not None else None), (color_weight if colors is not None else None)
+
+
+def tsdf_surface(tsdf, weight, color, color_weight, origin, voxel_size, min_weight):
+    """The zero crossings of a TSDF volume in ascending edge id (csrc/fm_torch.cpp: tsdf_surface_op -> fm_tsdf_surface_count, a cumulative
+    sum, fm_tsdf_surface_emit): (xyz, normals, rgb, edge) — rgb None without ``color``.  Waits for the device once, to size the output."""
+    xyz, normals, rgb, edge = torch_ops().tsdf_surface(tsdf, weight, color, color_weight, *(float(v) for v in origin), float(voxel_size), int(min_weight))
+    return xyz, normals, (rgb if color is not None else None), edge
 
 
 def softmin_intrinsics(depth, weights, bwd_flow, indices, candidate_k, rel, weight_sens, frames):

@@ -1290,6 +1290,151 @@ FM_HD void depth_consistency_pose(const float* e_i, const float* e_j, float* out
   out[15] = 1.f;
 }
 
+// ---------------------------------------------------------------------------------
+// TSDF fusion (export.tsdf_volume; fm_tsdf_volume.hip and its host twin both call these): ONE voxel against ONE frame, and ONE edge
+// of the finished volume.
+//   W_f    = E_f⁻¹ by inv4 in fp64, rounded once (tsdf_world_to_camera) — once per frame, handed back to the caller;
+//   centre c = origin + (index + 0.5)·voxel_size per axis (tsdf_centre);
+//   p = W_f·[c;1];  skipped unless p.z > near;  uv = project_camera_space(p, K_f) (ε = 1e-5, ±1e8 / NaN -> 0, as project_point);
+//   skipped unless 0 <= u, v < 1;  pixel = (min(floor(v·H), H−1), min(floor(u·W), W−1)) (the clamp of render_splat_at);
+//   d = depth there: skipped unless 0 < d < inf (and keep);  sdf = d − p.z: skipped when sdf < −truncation;
+//   t = min(sdf/truncation, 1);  coloured when sdf <= truncation.
+// A decision hangs on every rounding up to the floor and on the one of sdf, so they are WRITTEN OUT — contraction is off and the fused
+// multiply-adds are explicit — and BOTH builds evaluate this same form: under a host compiler __builtin_fmaf is libm's correctly
+// rounded fmaf, and every division here is IEEE in both.
+// ---------------------------------------------------------------------------------
+FM_HD void tsdf_world_to_camera(const float* e, float* out) {
+  double a[16], inv[16];
+  for (int i = 0; i < 16; ++i) a[i] = e[i];
+  inv4(a, inv);
+  for (int i = 0; i < 16; ++i) out[i] = (float)inv[i];
+}
+
+FM_HD float tsdf_centre(float origin, int index, float voxel_size) {
+  FM_NO_CONTRACT
+  const float offset = ((float)index + 0.5f) * voxel_size;
+  return origin + offset;
+}
+
+// -> the pixel (row·w + col) of frame f that voxel centre c projects into, −1 when the frame does not see it; pz = p.z either way.
+FM_HD int tsdf_pixel_of(const Pose& wc, const Mat3& k, const float c[3], float near, int h, int w, float& pz) {
+  FM_NO_CONTRACT
+  const float px = __builtin_fmaf(wc.r[2], c[2], __builtin_fmaf(wc.r[1], c[1], wc.r[0] * c[0])) + wc.t[0];
+  const float py = __builtin_fmaf(wc.r[5], c[2], __builtin_fmaf(wc.r[4], c[1], wc.r[3] * c[0])) + wc.t[1];
+  pz = __builtin_fmaf(wc.r[8], c[2], __builtin_fmaf(wc.r[7], c[1], wc.r[6] * c[0])) + wc.t[2];
+  if (!(pz > near)) return -1;
+  const float inv_s = 1.0f / (pz + kProjEps);
+  float pass;
+  const float q0 = nan_to_num(px * inv_s, pass), q1 = nan_to_num(py * inv_s, pass), q2 = nan_to_num(pz * inv_s, pass);
+  const float u = __builtin_fmaf(k.m[2], q2, __builtin_fmaf(k.m[1], q1, k.m[0] * q0));
+  const float v = __builtin_fmaf(k.m[5], q2, __builtin_fmaf(k.m[4], q1, k.m[3] * q0));
+  if (!(u >= 0.f && u < 1.f && v >= 0.f && v < 1.f)) return -1;
+  const int col = (int)floorf(u * (float)w), row = (int)floorf(v * (float)h);  // (u < 1 may still round to u·w == w: the clamp)
+  return (row < h - 1 ? row : h - 1) * w + (col < w - 1 ? col : w - 1);
+}
+
+// One depth sample against p.z -> taken?  t and `coloured` are set when it is.
+FM_HD bool tsdf_term(float d, float pz, float truncation, float& t, bool& coloured) {
+  FM_NO_CONTRACT
+  if (!(d > 0.f && d < __builtin_inff())) return false;
+  const float sdf = d - pz;
+  if (sdf < -truncation) return false;  // hidden behind the surface
+  const float q = sdf / truncation;
+  t = q < 1.f ? q : 1.f;
+  coloured = sdf <= truncation;
+  return true;
+}
+
+FM_HD float tsdf_finish(float sum, int weight) { return weight > 0 ? sum / (float)weight : 1.f; }
+
+// The finished volume as its edges see it: tsdf / weight (nz,ny,nx), color (nz,ny,nx,3) and color_weight or null.
+struct TsdfGrid {
+  const float* tsdf;
+  const int32_t* weight;
+  const float* color;
+  const int32_t* color_weight;
+  int nx, ny, nz;
+  int min_weight;
+  float origin[3];
+  float voxel_size;
+};
+
+FM_HD void tsdf_voxel_ijk(const TsdfGrid& g, long voxel, int ijk[3]) {
+  ijk[0] = (int)(voxel % g.nx);
+  const long rest = voxel / g.nx;
+  ijk[1] = (int)(rest % g.ny);
+  ijk[2] = (int)(rest / g.ny);
+}
+
+FM_HD long tsdf_axis_stride(const TsdfGrid& g, int axis) { return axis == 0 ? 1L : (axis == 1 ? (long)g.nx : (long)g.nx * g.ny); }
+FM_HD int tsdf_axis_size(const TsdfGrid& g, int axis) { return axis == 0 ? g.nx : (axis == 1 ? g.ny : g.nz); }
+// (selects, not an indexed load: with a run-time axis an indexed array of three would live in scratch memory on the device)
+FM_HD int tsdf_pick(const int v[3], int axis) { return axis == 0 ? v[0] : (axis == 1 ? v[1] : v[2]); }
+
+// Is the edge from `voxel` (a linear index inside the grid) to its +axis neighbour a zero crossing: the neighbour exists, both ends
+// have weight >= min_weight and exactly one of them is negative.
+FM_HD bool tsdf_edge_crosses(const TsdfGrid& g, long voxel, const int ijk[3], int axis) {
+  if (tsdf_pick(ijk, axis) + 1 >= tsdf_axis_size(g, axis)) return false;
+  const long other = voxel + tsdf_axis_stride(g, axis);
+  if (g.weight[voxel] < g.min_weight || g.weight[other] < g.min_weight) return false;
+  return (g.tsdf[voxel] < 0.f) != (g.tsdf[other] < 0.f);
+}
+
+// ∇tsdf at a voxel in units of 1/voxel: central differences over the neighbours that are inside the grid and observed
+// (weight >= min_weight), one-sided against the voxel itself where one is missing, 0 where both are.
+FM_HD void tsdf_gradient(const TsdfGrid& g, long voxel, const int ijk[3], float out[3]) {
+  FM_NO_CONTRACT
+  const float here = g.tsdf[voxel];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const long stride = tsdf_axis_stride(g, a);
+    const bool lo = ijk[a] > 0 && g.weight[voxel - stride] >= g.min_weight;
+    const bool hi = ijk[a] + 1 < tsdf_axis_size(g, a) && g.weight[voxel + stride] >= g.min_weight;
+    const float below = lo ? g.tsdf[voxel - stride] : here, above = hi ? g.tsdf[voxel + stride] : here;
+    const float diff = above - below;
+    out[a] = lo && hi ? 0.5f * diff : diff;
+  }
+}
+
+// The point of a crossing edge: s = t0/(t0 − t1), xyz = the low centre moved by s·voxel_size along the axis, the normal = the
+// normalised lerp by s of the two ends' gradients (zero if it has no length; it points up the field: out of the surface, toward the
+// cameras), rgb = the lerp of the two ends' mean colours, the one end that has any if only one does, else 0 (rgb is written with `with_color` only).
+FM_HD void tsdf_edge_point(const TsdfGrid& g, long voxel, const int ijk[3], int axis, bool with_color, float xyz[3], float normal[3], float rgb[3]) {
+  FM_NO_CONTRACT
+  const long other = voxel + tsdf_axis_stride(g, axis);
+  const float t0 = g.tsdf[voxel], t1 = g.tsdf[other];
+  const float s = t0 / (t0 - t1);
+  const float step = s * g.voxel_size;
+  int ijk1[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float centre = tsdf_centre(g.origin[a], ijk[a], g.voxel_size);
+    xyz[a] = a == axis ? centre + step : centre;
+    ijk1[a] = ijk[a] + (a == axis ? 1 : 0);
+  }
+  float g0[3], g1[3], n[3];
+  tsdf_gradient(g, voxel, ijk, g0);
+  tsdf_gradient(g, other, ijk1, g1);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float rise = s * (g1[a] - g0[a]);
+    n[a] = g0[a] + rise;
+  }
+  const float xx = n[0] * n[0], yy = n[1] * n[1], zz = n[2] * n[2];
+  const float length = sqrtf((xx + yy) + zz);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) normal[a] = length > 0.f ? n[a] / length : 0.f;
+  if (with_color) {
+    const bool has0 = g.color_weight[voxel] > 0, has1 = g.color_weight[other] > 0;
+  #pragma unroll
+  for (int a = 0; a < 3; ++a) {
+      const float c0 = g.color[voxel * 3 + a], c1 = g.color[other * 3 + a];
+      const float rise = s * (c1 - c0);
+      rgb[a] = has0 && has1 ? c0 + rise : (has0 ? c0 : (has1 ? c1 : 0.f));
+    }
+  }
+}
+
 
 // ---------------------------------------------------------------------------------
 // Dense Procrustes (`num_points: null`: every pixel of every pair is a correspondence,
@@ -1543,4 +1688,5 @@ FM_HD void dense_bwd_s(const DenseBwd& c, const float h[3], const float t[3], co
 #include "fm_depth_consistency_host.h"
 #include "fm_render_views_host.h"
 #include "fm_voxel_cloud_host.h"
+#include "fm_tsdf_volume_host.h"
 #endif

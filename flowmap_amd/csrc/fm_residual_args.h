@@ -1,5 +1,5 @@
 // Argument checks and size formulas of the residual entry points (include/flowmap_hip.h: fm_flow_residuals, fm_track_residuals,
-// fm_alignment_residuals, fm_focal_sweep, fm_depth_consistency, fm_render_views, fm_voxel_cloud and their size functions), stated ONCE: the device build (fm_*.hip) and the serial host build of
+// fm_alignment_residuals, fm_focal_sweep, fm_depth_consistency, fm_render_views, fm_voxel_cloud, fm_tsdf_volume, fm_tsdf_surface_count / _emit and their size functions), stated ONCE: the device build (fm_*.hip) and the serial host build of
 // the same ABI (fm_*_host.h) both call these, so the two refuse the same calls and size the same workspaces.  Plain C++, no HIP.
 // Device-only, and therefore not here: the 16-byte path's eligibility and the pointer alignment the kernels need (the host build reads
 // element by element and never touches the workspace).
@@ -191,6 +191,44 @@ static inline bool voxel_cloud_args_ok(const float* depth, const float* kinv, co
   if (min_count < 1 || capacity < 1 || capacity > kVoxelMaxCapacity) return false;
   // the records are 64-byte requests, the counters 8-byte words: both builds refuse a misaligned pointer
   return (reinterpret_cast<uintptr_t>(workspace) & 63) == 0 && (reinterpret_cast<uintptr_t>(counters) & 7) == 0;
+}
+
+// ---- TSDF volume ----
+constexpr int kTsdfTile = 256;              // voxels per workgroup of tsdf_integrate_kernel and of the two surface kernels (x fastest)
+constexpr long kTsdfMaxVoxels = 1L << 31;   // nx·ny·nz stays below this: a voxel index is an int32, an edge id (voxel·3 + axis) an int64
+static inline bool tsdf_dims_ok(int nx, int ny, int nz) {
+  return nx >= 1 && ny >= 1 && nz >= 1 && (long)nx * ny < kTsdfMaxVoxels && (long)nx * ny * nz < kTsdfMaxVoxels;
+}
+static inline long tsdf_blocks(long voxels) { return (voxels + kTsdfTile - 1) / kTsdfTile; }
+static inline bool tsdf_surface_blocks_args_ok(int nx, int ny, int nz, const long* blocks) { return blocks && tsdf_dims_ok(nx, ny, nz); }
+static inline bool tsdf_finite(float x) { return x > -__builtin_inff() && x < __builtin_inff(); }
+static inline bool tsdf_grid_ok(float ox, float oy, float oz, float voxel_size) {
+  return tsdf_finite(ox) && tsdf_finite(oy) && tsdf_finite(oz) && voxel_size > 0.f && voxel_size < __builtin_inff();
+}
+
+static inline bool tsdf_volume_args_ok(const float* depth, const float* k, const float* ext, const float* colors, const uint8_t* keep, int frames, int height,
+                                       int width, int first_frame, int count, float ox, float oy, float oz, int nx, int ny, int nz, float voxel_size,
+                                       float truncation, float near, const float* world_to_camera, const float* tsdf, const int32_t* weight,
+                                       const float* color, const int32_t* color_weight) {
+  (void)keep;  // (optional)
+  if (!(depth && k && ext && world_to_camera && tsdf && weight)) return false;
+  if ((colors != nullptr) != (color != nullptr) || (colors != nullptr) != (color_weight != nullptr)) return false;
+  if (!(frames >= 1 && frames <= kResMaxRows && res_frame_ok(height, width) && (long)frames * height * width < kRenderMaxSources)) return false;
+  if (!(first_frame >= 0 && count >= 1 && (long)first_frame + count <= frames)) return false;
+  if (!tsdf_dims_ok(nx, ny, nz) || !tsdf_grid_ok(ox, oy, oz, voxel_size)) return false;
+  return truncation > 0.f && truncation < __builtin_inff() && near >= 0.f && near < __builtin_inff();
+}
+
+static inline bool tsdf_surface_count_args_ok(const float* tsdf, const int32_t* weight, int nx, int ny, int nz, int min_weight, const int64_t* block_counts) {
+  return tsdf && weight && block_counts && tsdf_dims_ok(nx, ny, nz) && min_weight >= 1;
+}
+
+static inline bool tsdf_surface_emit_args_ok(const float* tsdf, const int32_t* weight, const float* color, const int32_t* color_weight, int nx, int ny, int nz,
+                                             float ox, float oy, float oz, float voxel_size, int min_weight, const int64_t* block_offsets, long rows,
+                                             const float* xyz, const float* normals, const float* rgb, const int64_t* edge) {
+  if (!(tsdf && weight && block_offsets && xyz && normals && edge)) return false;
+  if ((color != nullptr) != (color_weight != nullptr) || (color != nullptr) != (rgb != nullptr)) return false;
+  return tsdf_dims_ok(nx, ny, nz) && tsdf_grid_ok(ox, oy, oz, voxel_size) && min_weight >= 1 && rows >= 1;
 }
 
 }  // namespace fm

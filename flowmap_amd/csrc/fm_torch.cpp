@@ -52,7 +52,7 @@ using OptTensor = std::optional<Tensor>;
   X(fm_random_subset) X(fm_random_subset_stateful) X(fm_abi_version) X(fm_flow_loss_fused_taps) X(fm_track_loss_fused_fwd_taps) X(fm_tap_grad_apply) \
   X(fm_flow_loss_fused_bitmask) X(fm_flow_residuals) X(fm_flow_residual_blocks) X(fm_track_residuals) X(fm_track_residual_workspace) \
   X(fm_depth_consistency) X(fm_depth_consistency_blocks) X(fm_render_views) X(fm_render_views_workspace) \
-  X(fm_voxel_cloud) X(fm_voxel_cloud_workspace)
+  X(fm_voxel_cloud) X(fm_voxel_cloud_workspace) X(fm_tsdf_volume) X(fm_tsdf_surface_blocks) X(fm_tsdf_surface_count) X(fm_tsdf_surface_emit)
 
 struct Api {
 #define X(name) decltype(&::name) name = nullptr;
@@ -1759,6 +1759,82 @@ static std::vector<Tensor> voxel_cloud_op(const Tensor& depth_in, const Tensor& 
   return {xyz, rgb, count, first, slot, pixel_slot, counters};
 }
 
+// export.tsdf_volume (fm_tsdf_volume): the depth maps of a window of frames averaged into a truncated-signed-distance grid, one thread per
+// voxel.  Not differentiable.  -> {world_to_camera (F,4,4), tsdf (nz,ny,nx), weight int32, color (nz,ny,nx,3), color_weight int32 (both
+// empty without colors)}.  No workspace.
+static std::vector<Tensor> tsdf_volume_op(const Tensor& depth_in, const Tensor& k_in, const Tensor& ext_in, const OptTensor& colors_in, const OptTensor& keep_in,
+                                          int64_t first_frame, int64_t count, double ox, double oy, double oz, int64_t nx, int64_t ny, int64_t nz,
+                                          double voxel_size, double truncation, double near) {
+  at::NoGradGuard no_grad;
+  const bool has_colors = colors_in.has_value() && colors_in->defined(), has_keep = keep_in.has_value() && keep_in->defined();
+  const Tensor colors_t = has_colors ? *colors_in : Tensor(), keep_t = has_keep ? *keep_in : Tensor();
+  const auto dev = check_device({&depth_in, &k_in, &ext_in, &colors_t, &keep_t});
+  const Tensor depth = f32c(depth_in.detach(), "depths"), k = f32c(k_in.detach(), "intrinsics"), ext = f32c(ext_in.detach(), "extrinsics");
+  const Tensor colors = has_colors ? f32c(colors_t.detach(), "colors") : Tensor();
+  TORCH_CHECK(depth.dim() == 3, "flowmap_amd: depths must be (frame, height, width)");
+  const int64_t f = depth.size(0), h = depth.size(1), w = depth.size(2);
+  TORCH_CHECK(f >= 1 && f <= 65535 && h * w >= 1 && h * w < (int64_t(1) << 30) && f * h * w < (int64_t(1) << 31),
+              "flowmap_amd: tsdf_volume indexes pixels with int32 and takes at most 65 535 frames per call (got ", f, " x ", h, " x ", w, ")");
+  TORCH_CHECK(k.sizes() == at::IntArrayRef({f, 3, 3}) && ext.sizes() == at::IntArrayRef({f, 4, 4}), "flowmap_amd: intrinsics / extrinsics do not match the depths");
+  TORCH_CHECK(!has_colors || colors.sizes() == at::IntArrayRef({f, 3, h, w}), "flowmap_amd: colors must be (frame, 3, height, width)");
+  TORCH_CHECK(!has_keep || (keep_t.scalar_type() == at::kBool && keep_t.sizes() == depth.sizes()), "flowmap_amd: keep must be a bool tensor shaped like the depths");
+  const Tensor keep = has_keep ? keep_t.contiguous() : Tensor();
+  TORCH_CHECK(nx >= 1 && ny >= 1 && nz >= 1 && nx < (int64_t(1) << 31) && ny < (int64_t(1) << 31) && nz < (int64_t(1) << 31) && nx * ny < (int64_t(1) << 31) &&
+                  nx * ny * nz < (int64_t(1) << 31),
+              "flowmap_amd: tsdf_volume: dims must be >= 1 with nx * ny * nz < 2^31 (got ", nx, " x ", ny, " x ", nz, ")");
+  const auto fopt = depth.options();
+  Tensor w2c = at::empty({f, 4, 4}, fopt), tsdf = at::empty({nz, ny, nx}, fopt), weight = at::empty({nz, ny, nx}, fopt.dtype(at::kInt));
+  Tensor color = has_colors ? at::empty({nz, ny, nx, 3}, fopt) : at::empty({0}, fopt);
+  Tensor color_weight = has_colors ? at::empty({nz, ny, nx}, fopt.dtype(at::kInt)) : at::empty({0}, fopt.dtype(at::kInt));
+  DeviceScope scope(dev);
+  FM_CALL(fm_tsdf_volume, ptr(depth), ptr(k), ptr(ext), has_colors ? ptr(colors) : nullptr, has_keep ? ptr<uint8_t>(keep) : nullptr, (int)f, (int)h, (int)w,
+          (int)first_frame, (int)count, (float)ox, (float)oy, (float)oz, (int)nx, (int)ny, (int)nz, (float)voxel_size, (float)truncation, (float)near, ptr(w2c),
+          ptr(tsdf), ptr<int32_t>(weight), has_colors ? ptr(color) : nullptr, has_colors ? ptr<int32_t>(color_weight) : nullptr, scope.stream);
+  return {w2c, tsdf, weight, color, color_weight};
+}
+
+// TsdfVolume.surface_points (fm_tsdf_surface_count, fm_tsdf_surface_emit): the zero crossings of a volume in ascending edge id.  -> {xyz,
+// normals, rgb (empty without color), edge int64}.  The count pass, an exclusive cumulative sum of the per-workgroup counts and the read of
+// their total (the one synchronisation: it sizes the output), then the emit pass.
+static std::vector<Tensor> tsdf_surface_op(const Tensor& tsdf_in, const Tensor& weight_in, const OptTensor& color_in, const OptTensor& color_weight_in, double ox,
+                                           double oy, double oz, double voxel_size, int64_t min_weight) {
+  at::NoGradGuard no_grad;
+  const bool has_color = color_in.has_value() && color_in->defined();
+  TORCH_CHECK(has_color == (color_weight_in.has_value() && color_weight_in->defined()), "flowmap_amd: surface_points: color and color_weight go together");
+  const Tensor color_t = has_color ? *color_in : Tensor(), cw_t = has_color ? *color_weight_in : Tensor();
+  const auto dev = check_device({&tsdf_in, &weight_in, &color_t, &cw_t});
+  const Tensor tsdf = f32c(tsdf_in.detach(), "tsdf");
+  TORCH_CHECK(tsdf.dim() == 3 && weight_in.scalar_type() == at::kInt && weight_in.sizes() == tsdf.sizes(),
+              "flowmap_amd: surface_points: tsdf must be (nz, ny, nx) float32 and weight int32 of the same shape");
+  const Tensor weight = weight_in.contiguous();
+  const int64_t nz = tsdf.size(0), ny = tsdf.size(1), nx = tsdf.size(2);
+  TORCH_CHECK(nx >= 1 && ny >= 1 && nz >= 1 && nx * ny * nz < (int64_t(1) << 31), "flowmap_amd: surface_points: the grid must hold 1 to 2^31 - 1 voxels");
+  Tensor color, cw;
+  if (has_color) {
+    color = f32c(color_t.detach(), "color");
+    TORCH_CHECK(color.sizes() == at::IntArrayRef({nz, ny, nx, 3}) && cw_t.scalar_type() == at::kInt && cw_t.sizes() == tsdf.sizes(),
+                "flowmap_amd: surface_points: color must be (nz, ny, nx, 3) float32 and color_weight int32 shaped like tsdf");
+    cw = cw_t.contiguous();
+  }
+  long blocks = 0;
+  FM_CALL(fm_tsdf_surface_blocks, (int)nx, (int)ny, (int)nz, &blocks);
+  const auto fopt = tsdf.options();
+  Tensor counts = at::empty({(int64_t)blocks}, fopt.dtype(at::kLong));
+  DeviceScope scope(dev);
+  FM_CALL(fm_tsdf_surface_count, ptr(tsdf), ptr<int32_t>(weight), (int)nx, (int)ny, (int)nz, (int)min_weight, ptr<int64_t>(counts), scope.stream);
+  const Tensor ends = at::cumsum(counts, 0);
+  const int64_t rows = ends[blocks - 1].item<int64_t>();
+  Tensor xyz = at::empty({rows, 3}, fopt), normals = at::empty({rows, 3}, fopt), rgb = has_color ? at::empty({rows, 3}, fopt) : at::empty({0}, fopt);
+  Tensor edge = at::empty({rows}, fopt.dtype(at::kLong));
+  if (rows > 0) {
+    const Tensor offsets = (ends - counts).contiguous();
+    FM_CALL(fm_tsdf_surface_emit, ptr(tsdf), ptr<int32_t>(weight), has_color ? ptr(color) : nullptr, has_color ? ptr<int32_t>(cw) : nullptr, (int)nx, (int)ny,
+            (int)nz, (float)ox, (float)oy, (float)oz, (float)voxel_size, (int)min_weight, ptr<int64_t>(offsets), (long)rows, ptr(xyz), ptr(normals),
+            has_color ? ptr(rgb) : nullptr, ptr<int64_t>(edge), scope.stream);
+  }
+  return {xyz, normals, rgb, edge};
+}
+
 }  // namespace fmt
 
 TORCH_LIBRARY(flowmap_amd, m) {
@@ -1848,4 +1924,9 @@ TORCH_LIBRARY(flowmap_amd, m) {
         fmt::render_views_op);
   m.def("voxel_cloud(Tensor depth, Tensor kinv, Tensor ext, Tensor? colors, Tensor? keep, float voxel_size, int min_count, int capacity, bool details) -> Tensor[]",
         fmt::voxel_cloud_op);
+  m.def("tsdf_volume(Tensor depth, Tensor k, Tensor ext, Tensor? colors, Tensor? keep, int first_frame, int count, float ox, float oy, float oz, int nx, int ny, "
+        "int nz, float voxel_size, float truncation, float near) -> Tensor[]",
+        fmt::tsdf_volume_op);
+  m.def("tsdf_surface(Tensor tsdf, Tensor weight, Tensor? color, Tensor? color_weight, float ox, float oy, float oz, float voxel_size, int min_weight) -> Tensor[]",
+        fmt::tsdf_surface_op);
 }

@@ -5,6 +5,8 @@
   point-major), as ONE launch (fm_world_points) instead of F × (unproject + einsum + 2 copies).
 * ``voxel_point_cloud``: the same points merged per cell of a world-space grid — one averaged point and colour per occupied voxel, a
   count and the lowest contributing pixel —, in ONE pass over depth (fm_voxel_cloud) with no point cloud formed; bit-reproducible.
+* ``tsdf_volume``: the depth maps fused into a truncated-signed-distance grid (fm_tsdf_volume: one thread per voxel walks the frames, no
+  atomics) -> ``TsdfVolume``, whose ``surface_points`` are the zero crossings with normals; ``grid_around`` sizes the grid from a cloud.
 * ``write_ply``: the vertex layout of colmap.py:31-53 (x y z nx ny nz red green blue, binary
   little-endian — what 3D Gaussian Splatting reads), written with numpy alone.
 * ``compute_ate``: flowmap/misc/ate.py:7-25 (scipy Procrustes alignment, RMS over all
@@ -23,8 +25,9 @@ import torch
 from torch import Tensor
 
 from . import _ops
+from ._base import parse_window
 from ._lib import call, check_device, ptr, stream_for
-from .types import VoxelCloud
+from .types import TsdfVolume, VoxelCloud
 
 VOXEL_MAX_CAPACITY = 1 << 28  # (fm_residual_args.h: kVoxelMaxCapacity)
 
@@ -133,15 +136,94 @@ def voxel_point_cloud(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, co
     return VoxelCloud(xyz, rgb, count, first, {"masked": masked, "invalid": invalid, "out_of_range": out_of_range}, voxel_of, float(voxel_size))
 
 
+TSDF_MAX_VOXELS = 1 << 31  # (fm_residual_args.h: kTsdfMaxVoxels)
+
+
+def _f32_number(value, what: str, name: str, *, positive: bool = False, minimum: Optional[float] = None) -> float:
+    """A Python number as the float32 the kernels take -> that float32's value as a float; a bool, a non-number, a non-finite value (after
+    rounding to float32 too) or one out of range raises ValueError naming the argument."""
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError(f"flowmap_amd: {what}: {name} must be a number (got {value!r})")
+    with np.errstate(over="ignore"):
+        rounded = float(np.float32(value))
+    if not np.isfinite(rounded) or (positive and not rounded > 0.0) or (minimum is not None and not rounded >= minimum):
+        bound = "> 0" if positive else (f">= {minimum:g}" if minimum is not None else "finite")
+        raise ValueError(f"flowmap_amd: {what}: {name} must be a finite float32 {bound} (got {value!r})")
+    return rounded
+
+
+def grid_around(points, voxel_size: float, margin: float = 0.0) -> Tuple[Tuple[float, float, float], Tuple[int, int, int]]:
+    """The grid of edge ``voxel_size`` that encloses a VoxelCloud's centroids or an (N, 3) tensor of points with ``margin`` world units to
+    spare on every side -> (origin, dims) for ``tsdf_volume``.  Non-finite points are ignored; the minimum and maximum are taken with
+    torch (plumbing over a small cloud) and read back once."""
+    what = "grid_around"
+    voxel_size = _f32_number(voxel_size, what, "voxel_size", positive=True)
+    margin = _f32_number(margin, what, "margin", minimum=0.0)
+    xyz = points.xyz if isinstance(points, VoxelCloud) else points
+    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3 or not xyz.is_floating_point():
+        raise ValueError(f"flowmap_amd: {what}: points must be a VoxelCloud or a floating (N, 3) tensor (got {getattr(xyz, 'shape', type(xyz).__name__)})")
+    with torch.no_grad():
+        xyz = xyz.detach().double()
+        xyz = xyz[torch.isfinite(xyz).all(dim=1)]
+        if xyz.shape[0] == 0:
+            raise ValueError(f"flowmap_amd: {what}: points holds no finite point")
+        low, high = xyz.min(dim=0).values.cpu() - margin, xyz.max(dim=0).values.cpu() + margin
+    origin = tuple(float(np.float32(v)) for v in low.tolist())
+    dims = tuple(max(1, int(np.ceil((hi - lo) / voxel_size)) + 1) for lo, hi in zip(origin, high.tolist()))  # (+1: the rounding of the origin and of the last cell)
+    if dims[0] * dims[1] * dims[2] >= TSDF_MAX_VOXELS:
+        raise ValueError(f"flowmap_amd: {what}: {dims[0]} x {dims[1]} x {dims[2]} voxels at voxel_size = {voxel_size!r} do not fit 2^31: pass a larger voxel_size")
+    return origin, dims
+
+
+def tsdf_volume(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, colors: Optional[Tensor], voxel_size: float, *, origin, dims,
+                truncation: Optional[float] = None, near: float = 0.0, keep: Optional[Tensor] = None, frames=None) -> TsdfVolume:
+    """The depth maps (arguments and checks of ``world_point_cloud``) fused into a truncated-signed-distance grid -> TsdfVolume.
+
+    ``origin``: the world position of the low corner of voxel (0, 0, 0), 3 numbers; ``dims`` = (nx, ny, nz), each >= 1, fewer than 2^31
+    voxels in all (``grid_around`` gives both for a cloud).  Voxel (i, j, k) has its centre at ``origin + (index + 0.5)·voxel_size``.  For
+    each frame of the window ``frames`` (None: all; a slice with step 1; (first, count)), in ascending order, the centre is moved into the
+    camera (p = E_f⁻¹·c), skipped unless ``p.z > near``, projected, skipped unless it lands inside the frame, and compared with the depth d
+    of the pixel it lands in (skipped where d is not finite, d <= 0 or ``keep`` is False): sdf = d − p.z; a voxel more than ``truncation``
+    (default 4·voxel_size) behind the surface is hidden and skipped; otherwise min(sdf/truncation, 1) enters the voxel's mean and, where
+    sdf <= truncation, the pixel's colour its mean colour.  One HIP pass, one thread per voxel, sums in registers in frame order: no
+    atomics, and the result is bit-reproducible.  Never differentiable; reads its arguments and nothing else."""
+    what = "tsdf_volume"
+    f, h, w = _check_cloud_arguments(depths, intrinsics, extrinsics, colors, keep)
+    voxel_size = _f32_number(voxel_size, what, "voxel_size", positive=True)
+    truncation = _f32_number(4.0 * voxel_size if truncation is None else truncation, what, "truncation", positive=True)
+    near = _f32_number(near, what, "near", minimum=0.0)
+    if isinstance(origin, (str, bytes)) or not hasattr(origin, "__len__") or len(origin) != 3:
+        raise ValueError(f"flowmap_amd: {what}: origin must be 3 numbers (got {origin!r})")
+    origin = tuple(_f32_number(v.item() if torch.is_tensor(v) else v, what, "origin") for v in origin)
+    if isinstance(dims, (str, bytes)) or not hasattr(dims, "__len__") or len(dims) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in dims):
+        raise ValueError(f"flowmap_amd: {what}: dims must be 3 integers (nx, ny, nz) (got {dims!r})")
+    dims = tuple(int(v) for v in dims)
+    if min(dims) < 1 or dims[0] * dims[1] * dims[2] >= TSDF_MAX_VOXELS:
+        raise ValueError(f"flowmap_amd: {what}: dims must each be >= 1 with nx * ny * nz < 2^31 (got {dims!r})")
+    if f > 65535 or h * w >= 1 << 30 or f * h * w >= 1 << 31:
+        raise ValueError(f"flowmap_amd: {what}: frames x height x width = {f} x {h} x {w} does not fit (at most 65535 frames, int32 pixel indices)")
+    first, count = parse_window(frames, f, what, "frames")
+    with torch.no_grad():
+        w2c, tsdf, weight, color, color_weight = _ops.tsdf_volume(depths, _ops._f32c(intrinsics.detach(), "intrinsics"), extrinsics, colors, keep, first, count,
+                                                                  origin, dims, voxel_size, truncation, near)
+    return TsdfVolume(tsdf, weight, color, color_weight, w2c, origin, voxel_size, truncation, near, (first, count))
+
+
 _PLY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
                        ("red", "u1"), ("green", "u1"), ("blue", "u1")])
 
 
-def write_ply(path: Path, xyz: np.ndarray, rgb: np.ndarray) -> None:
-    """colmap.py:31-53: zero normals, colours scaled by 255 and truncated to uint8."""
+def write_ply(path: Path, xyz: np.ndarray, rgb: np.ndarray, normals: Optional[np.ndarray] = None) -> None:
+    """colmap.py:31-53: zero normals, colours scaled by 255 and truncated to uint8.  ``normals`` (N, 3): written as nx ny nz instead of the
+    zeros (TsdfVolume.write_ply); without them the file is what it always was."""
     xyz = np.asarray(xyz, dtype=np.float32)
     vertices = np.zeros(xyz.shape[0], dtype=_PLY_DTYPE)
     vertices["x"], vertices["y"], vertices["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if normals is not None:
+        normals = np.asarray(normals, dtype=np.float32)
+        if normals.shape != xyz.shape:
+            raise ValueError(f"flowmap_amd: write_ply: normals of shape {normals.shape} do not match the points {xyz.shape}")
+        vertices["nx"], vertices["ny"], vertices["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     scaled = (np.asarray(rgb) * 255).astype(np.float32)
     vertices["red"], vertices["green"], vertices["blue"] = scaled[:, 0], scaled[:, 1], scaled[:, 2]
     kinds = {"<f4": "float", "|u1": "uchar"}

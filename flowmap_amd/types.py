@@ -12,6 +12,7 @@
   DepthConsistency  what projection.depth_consistency / Model.consistency return (likewise: the reference never compares its depth maps)
   RenderedViews  what projection.render_views / Model.render return (likewise: the reference never renders its reconstruction)
   VoxelCloud  what export.voxel_point_cloud / Model.point_cloud return (likewise: the reference exports every pixel as a point)
+  TsdfVolume  what export.tsdf_volume / Model.tsdf return (likewise: the reference has no surface, only per-pixel points)
 
 The reference's own dataclasses are accepted everywhere these are (duck typing): the
 drop-in never checks the class, only the attribute names.
@@ -262,3 +263,48 @@ class VoxelCloud:
 
         xyz = self.xyz.detach().cpu().numpy()
         write_ply(path, xyz, (torch.zeros_like(self.xyz) if self.rgb is None else self.rgb).detach().cpu().numpy())
+
+
+@dataclass
+class TsdfVolume:
+    """The depth maps fused into a truncated-signed-distance grid — export.tsdf_volume / Model.tsdf.  Voxel (i, j, k) is element
+    [k, j, i] of every field; its centre is ``origin + (index + 0.5)·voxel_size`` per axis.  ``tsdf`` is the mean over the frames that see
+    the voxel of min(sdf/truncation, 1) — positive in front of the surface, toward the cameras —, exactly 1 where ``weight`` is 0."""
+
+    tsdf: Tensor  # (nz, ny, nx) float32
+    weight: Tensor  # (nz, ny, nx) int32: the frames that contributed
+    color: Optional[Tensor]  # (nz, ny, nx, 3) float32: the mean colour over the frames with sdf <= truncation; None without colors
+    color_weight: Optional[Tensor]  # (nz, ny, nx) int32; None without colors
+    world_to_camera: Tensor  # (F, 4, 4) float32: E_f⁻¹ as the pass used it, for every frame of the video
+    origin: tuple  # 3 floats (as rounded to float32): the low corner of voxel (0, 0, 0)
+    voxel_size: float
+    truncation: float
+    near: float
+    frames: tuple  # (first, count): the window of frames that was fused
+
+    @property
+    def dims(self) -> tuple:
+        """(nx, ny, nz)"""
+        nz, ny, nx = self.tsdf.shape
+        return int(nx), int(ny), int(nz)
+
+    def surface_points(self, min_weight: int = 1):
+        """The zero crossings of the volume as an oriented point set -> (xyz (M,3), normals (M,3), rgb (M,3) or None, edge (M,) int64), rows
+        in ascending ``edge`` = voxel_linear_index·3 + axis: the edge from a voxel to its +x, +y or +z neighbour crosses when both ends have
+        ``weight >= min_weight`` and exactly one tsdf is negative.  The point lies at s = t0/(t0 − t1) along the edge; the normal is the
+        normalised lerp of the ends' gradients (out of the surface, toward the cameras; zero where the gradient vanishes); rgb the lerp of
+        the ends' colours.  Two HIP passes, count and emit, around one cumulative sum: no atomics, no sort, no capacity; bit-reproducible."""
+        from . import _ops
+
+        if isinstance(min_weight, bool) or not isinstance(min_weight, int) or not 1 <= min_weight < 1 << 31:
+            raise ValueError(f"flowmap_amd: surface_points: min_weight must be an integer >= 1 (got {min_weight!r})")
+        with torch.no_grad():
+            return _ops.tsdf_surface(self.tsdf, self.weight, self.color, self.color_weight, self.origin, self.voxel_size, min_weight)
+
+    def write_ply(self, path, min_weight: int = 1) -> None:
+        """export.write_ply of ``surface_points(min_weight)`` with their normals (black without colours)."""
+        from .export import write_ply
+
+        xyz, normals, rgb, _ = self.surface_points(min_weight)
+        rgb = torch.zeros_like(xyz) if rgb is None else rgb
+        write_ply(path, xyz.cpu().numpy(), rgb.cpu().numpy(), normals.cpu().numpy())

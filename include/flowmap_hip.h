@@ -48,9 +48,10 @@ extern "C" {
  * pair — fm_focal_sweep; the existing entries are unchanged; version 13: the depth consistency across frame offsets —
  * fm_depth_consistency / fm_depth_consistency_blocks; the existing entries are unchanged; version 14: the rendered views —
  * fm_render_views / fm_render_views_workspace; the existing entries are unchanged; version 15: the voxel-fused point cloud —
- * fm_voxel_cloud / fm_voxel_cloud_workspace; the existing entries are unchanged).  A binding checks
+ * fm_voxel_cloud / fm_voxel_cloud_workspace; the existing entries are unchanged; version 16: the TSDF volume and its surface points —
+ * fm_tsdf_volume, fm_tsdf_surface_blocks / fm_tsdf_surface_count / fm_tsdf_surface_emit; the existing entries are unchanged).  A binding checks
  * fm_abi_version() == FM_ABI_VERSION when it loads the library. */
-#define FM_ABI_VERSION 15
+#define FM_ABI_VERSION 16
 int fm_abi_version(void);
 
 #define FM_STAT_STRIDE 16      /* doubles per pair in `stats` */
@@ -964,6 +965,44 @@ int fm_voxel_cloud_workspace(long capacity, long* slots, long* bytes);
 int fm_voxel_cloud(const float* depth, const float* kinv, const float* ext, const float* colors, const uint8_t* keep, int frames, int height,
                    int width, double voxel_size, int min_count, long capacity, float* xyz, float* rgb, int32_t* count, int64_t* first,
                    int32_t* slot, int32_t* pixel_slot, unsigned long long* counters, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * TSDF fusion (ABI version 16): the depth maps averaged into a truncated-signed-distance grid — a GATHER: one thread per voxel walks the
+ * frames in ascending order, no atomics, every output written once, bit-reproducible.  Voxel (i,j,k), linear index (k·ny + j)·nx + i:
+ *   centre c = origin + (index + 0.5)·voxel_size per axis, fp32;  W_f = E_f^-1 (Gauss-Jordan in fp64, rounded once; written to
+ *   world_to_camera for ALL `frames` frames);  for f in [first_frame, first_frame + count), ascending:
+ *     p = W_f·[c;1]; skipped unless p.z > near; uv = K_f·(p / (p.z + 1e-5)) (+-1e8 / NaN -> 0); skipped unless 0 <= u,v < 1;
+ *     pixel (min(floor(v·H), H-1), min(floor(u·W), W-1)); d = depth there; skipped unless 0 < d < inf and keep (when given) != 0;
+ *     sdf = d - p.z; skipped when sdf < -truncation; else sum += min(sdf/truncation, 1), weight += 1, and, with colors and
+ *     sdf <= truncation, the three colour sums take the pixel's colour and color_weight += 1  (fm_math.h: tsdf_pixel_of, tsdf_term —
+ *     the fused multiply-adds are written out, both builds evaluate the same form);
+ *   tsdf = sum/weight, exactly 1 where weight == 0; color = sums/color_weight, 0 where color_weight == 0.
+ *   depth (F,H,W), k (F,3,3) normalised intrinsics (NOT their inverse), ext (F,4,4) camera-to-world, colors (F,3,H,W) or NULL, keep
+ *   (F,H,W) bytes or NULL: dense.  1 <= F <= 65535, H·W < 2^30, F·H·W < 2^31; 0 <= first_frame, count >= 1, first_frame + count <= F;
+ *   nx, ny, nz >= 1 with nx·ny·nz < 2^31; origin finite; voxel_size, truncation finite and > 0; near finite and >= 0.
+ *   world_to_camera (F,4,4) out; tsdf (nz,ny,nx) float, weight (nz,ny,nx) int32; color (nz,ny,nx,3) float and color_weight (nz,ny,nx)
+ *   int32: given exactly when colors is.
+ * Launches: one thread per frame for the poses, then one thread per voxel, 256 voxels per workgroup (x fastest).
+ *
+ * The zero crossings of a volume as oriented points, in ascending edge id = voxel·3 + axis (the edge from a voxel to its +x, +y, +z
+ * neighbour inside the grid): a crossing has weight >= min_weight at both ends and exactly one negative tsdf (fm_math.h:
+ * tsdf_edge_crosses, tsdf_edge_point).  A workgroup owns 256 consecutive voxels:
+ *   fm_tsdf_surface_blocks: blocks[0] (HOST long) = the workgroups of a grid, ceil(nx·ny·nz / 256);
+ *   fm_tsdf_surface_count: block_counts (blocks) int64 out = the crossings of each workgroup's voxels;
+ *   fm_tsdf_surface_emit: block_offsets (blocks) int64 in = the exclusive cumulative sum of block_counts; rows >= 1 = their total, the
+ *     rows of xyz (rows,3), normals (rows,3), rgb (rows,3; given exactly when color and color_weight are), edge (rows) int64; a row at
+ *     or past `rows` is not written.  s = t0/(t0 - t1); xyz = the low voxel's centre + s·voxel_size along the axis; normal = the
+ *     normalised lerp by s of the two ends' gradients (central differences over observed neighbours, one-sided where one is missing,
+ *     0 where both are; the zero vector if the lerp has no length); rgb = the lerp of the ends' colours (the one end with
+ *     color_weight > 0 if only one has, else 0).  min_weight >= 1.  No atomics, no sort. */
+int fm_tsdf_volume(const float* depth, const float* k, const float* ext, const float* colors, const uint8_t* keep, int frames, int height, int width,
+                   int first_frame, int count, float ox, float oy, float oz, int nx, int ny, int nz, float voxel_size, float truncation, float near,
+                   float* world_to_camera, float* tsdf, int32_t* weight, float* color, int32_t* color_weight, void* stream);
+int fm_tsdf_surface_blocks(int nx, int ny, int nz, long* blocks);
+int fm_tsdf_surface_count(const float* tsdf, const int32_t* weight, int nx, int ny, int nz, int min_weight, int64_t* block_counts, void* stream);
+int fm_tsdf_surface_emit(const float* tsdf, const int32_t* weight, const float* color, const int32_t* color_weight, int nx, int ny, int nz, float ox,
+                         float oy, float oz, float voxel_size, int min_weight, const int64_t* block_offsets, long rows, float* xyz, float* normals,
+                         float* rgb, int64_t* edge, void* stream);
 
 #ifdef __cplusplus
 }
