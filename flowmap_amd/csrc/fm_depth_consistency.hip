@@ -203,7 +203,6 @@ int fm_depth_consistency(const float* depth, const float* k, const float* kinv, 
   FM_CHECK_ARG(depth_consistency_args_ok(depth, k, kinv, ext, offsets, n_offsets, batch, frames, height, width, first_frame, count, tolerance, error, code,
                                          positions, reprojected, sampled, support, frame_sum, frame_valid, rel, workspace));
   const bool sums = frame_sum != nullptr;
-  auto aligned = [](const void* q, uintptr_t to) { return (reinterpret_cast<uintptr_t>(q) & (to - 1)) == 0; };
   FM_CHECK_ARG(!sums || aligned(workspace, 16));
   const long n = (long)height * width;
   ConsistencyParams p{depth, k, kinv, rel, error, code, positions, reprojected, sampled, support, workspace};

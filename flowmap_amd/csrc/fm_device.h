@@ -143,6 +143,11 @@ __device__ __forceinline__ void pose_chain_one_wave(const float* r, int steps, f
   }
 }
 
+// Host side, for the launchers (the extern "C" tails of fm_*.hip): `q` can be accessed in requests of `bytes` (a power of two; 16: float4)
+static inline bool aligned(const void* q, uintptr_t bytes = 16) { return (reinterpret_cast<uintptr_t>(q) & (bytes - 1)) == 0; }
+// Adam's decay rates (fm_optim.hip and the in-pass update of fm_flow.hip)
+static inline bool adam_betas_ok(double beta1, double beta2) { return beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0; }
+
 }  // namespace fm
 
 #define FM_OK 0

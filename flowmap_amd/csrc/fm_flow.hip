@@ -23,6 +23,7 @@
 #include "../../include/flowmap_hip.h"
 #include "fm_device.h"
 #include "fm_pose.h"
+#include "fm_residual_args.h"
 
 namespace fm {
 
@@ -837,17 +838,8 @@ static int flow_loss_launch(const float* depth, const float* k, const float* kin
   const bool grad = scale != nullptr;
   FlowParams p{depth, k, kinv, t_fwd, t_bwd, flow_fwd, flow_bwd, mask_fwd, mask_bwd, packed, scale, grad_depth, acc,
                frames, height, width, mapping_kind, delta, aspect_x, aspect_y, items_per_thread > 0 ? items_per_thread : 4};
-  {  // element strides of the five image stacks (dense unless the caller described a view)
-    const long n1 = (long)height * width;
-    const long per_frame[5] = {n1, 2 * n1, 2 * n1, n1, n1};
-    const long frames_of[5] = {frames, frames - 1, frames - 1, frames - 1, frames - 1};
-    for (int i = 0; i < 5; ++i) {
-      const bool given = layouts && (layouts[i].frame_stride != 0 || layouts[i].batch_stride != 0);
-      p.fs[i] = given ? layouts[i].frame_stride : per_frame[i];
-      p.bs[i] = given ? layouts[i].batch_stride : per_frame[i] * frames_of[i];
-      FM_CHECK_ARG(p.fs[i] >= per_frame[i] && (batch == 1 || p.bs[i] >= p.fs[i] * (frames_of[i] - 1) + per_frame[i]));
-    }
-  }
+  // element strides of the five image stacks (dense unless the caller described a view)
+  FM_CHECK_ARG(flow_strides(layouts, batch, frames, (long)height * width, p.fs, p.bs));
   if (adam) {
     p.depth_rw = const_cast<float*>(depth);
     p.exp_avg = adam->exp_avg;
@@ -865,7 +857,6 @@ static int flow_loss_launch(const float* depth, const float* k, const float* kin
   }
   // (`acc` is zero on entry: fm_flow_loss_finalize clears what it has read, so a workspace kept across steps never
   // needs a memset launch)
-  auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   const bool use_packed = packed != nullptr;
   bool strides16 = true;  // every frame of a view starts on a 16-byte boundary (the 16-byte path's loads)
   for (int i = 0; i < (use_packed ? 1 : 5); ++i) strides16 = strides16 && p.fs[i] % 4 == 0 && p.bs[i] % 4 == 0;
@@ -945,6 +936,15 @@ static int flow_loss_launch(const float* depth, const float* k, const float* kin
   FM_LAUNCH_STATUS();
 }
 
+// The Adam arguments of the in-pass update, checked -> `adam`; false: the call is refused.
+static bool flow_adam_args(FlowAdam& adam, float* exp_avg, float* exp_avg_sq, const uint8_t* touched, const float* scale, const float* grad_depth, int width,
+                           long step, double lr, double beta1, double beta2, double eps) {
+  if (!(exp_avg && exp_avg_sq && touched && scale && grad_depth && step >= 1 && width % 4 == 0)) return false;
+  if (!(adam_betas_ok(beta1, beta2) && aligned(exp_avg) && aligned(exp_avg_sq))) return false;
+  adam = FlowAdam{exp_avg, exp_avg_sq, touched, adam_coefficients((double)step, lr, beta1, beta2, eps, 0.0)};
+  return true;
+}
+
 int fm_flow_loss_fused(const float* depth, const float* k, const float* kinv, const float* t_fwd, const float* t_bwd,
                        const float* flow_fwd, const float* flow_bwd, const float* mask_fwd, const float* mask_bwd,
                        const float* packed, const float* scale, int batch, int frames, int height, int width,
@@ -968,11 +968,8 @@ int fm_flow_loss_fused_adam(float* depth, const float* k, const float* kinv, con
                             int batch, int frames, int height, int width, int mapping_kind, float delta, float aspect_x, float aspect_y,
                             float* grad_depth, double* acc, int items_per_thread, float* exp_avg, float* exp_avg_sq, const uint8_t* touched,
                             long step, double lr, double beta1, double beta2, double eps, void* stream) {
-  FM_CHECK_ARG(exp_avg && exp_avg_sq && touched && scale && grad_depth && step >= 1 && width % 4 == 0);
-  FM_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0);
-  auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  FM_CHECK_ARG(aligned(exp_avg) && aligned(exp_avg_sq));
-  const FlowAdam adam{exp_avg, exp_avg_sq, touched, adam_coefficients((double)step, lr, beta1, beta2, eps, 0.0)};
+  FlowAdam adam;
+  FM_CHECK_ARG(flow_adam_args(adam, exp_avg, exp_avg_sq, touched, scale, grad_depth, width, step, lr, beta1, beta2, eps));
   return flow_loss_launch(depth, k, kinv, t_fwd, t_bwd, flow_fwd, flow_bwd, mask_fwd, mask_bwd, packed, scale, batch, frames, height, width,
                           mapping_kind, delta, aspect_x, aspect_y, grad_depth, acc, items_per_thread, &adam, nullptr, stream);
 }
@@ -983,18 +980,11 @@ int fm_flow_loss_fused_taps(float* depth, const float* k, const float* kinv, con
                             float* grad_depth, double* acc, int items_per_thread, const fm_flow_taps* taps, float* exp_avg, float* exp_avg_sq,
                             const uint8_t* touched, long step, double lr, double beta1, double beta2, double eps, void* stream) {
   FM_CHECK_ARG(taps != nullptr);
-  if (exp_avg == nullptr) {
-    FM_CHECK_ARG(exp_avg_sq == nullptr && touched == nullptr);
-    return flow_loss_launch(depth, k, kinv, t_fwd, t_bwd, flow_fwd, flow_bwd, mask_fwd, mask_bwd, packed, scale, batch, frames, height, width,
-                            mapping_kind, delta, aspect_x, aspect_y, grad_depth, acc, items_per_thread, nullptr, nullptr, stream, taps);
-  }
-  FM_CHECK_ARG(exp_avg_sq && touched && scale && grad_depth && step >= 1 && width % 4 == 0);
-  FM_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0);
-  auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  FM_CHECK_ARG(aligned(exp_avg) && aligned(exp_avg_sq));
-  const FlowAdam adam{exp_avg, exp_avg_sq, touched, adam_coefficients((double)step, lr, beta1, beta2, eps, 0.0)};
+  FlowAdam adam;  // (no exp_avg: no update in the pass)
+  if (exp_avg == nullptr) FM_CHECK_ARG(exp_avg_sq == nullptr && touched == nullptr);
+  else FM_CHECK_ARG(flow_adam_args(adam, exp_avg, exp_avg_sq, touched, scale, grad_depth, width, step, lr, beta1, beta2, eps));
   return flow_loss_launch(depth, k, kinv, t_fwd, t_bwd, flow_fwd, flow_bwd, mask_fwd, mask_bwd, packed, scale, batch, frames, height, width,
-                          mapping_kind, delta, aspect_x, aspect_y, grad_depth, acc, items_per_thread, &adam, nullptr, stream, taps);
+                          mapping_kind, delta, aspect_x, aspect_y, grad_depth, acc, items_per_thread, exp_avg ? &adam : nullptr, nullptr, stream, taps);
 }
 
 int fm_flow_loss_fused_bitmask(float* depth, const float* k, const float* kinv, const float* t_fwd, const float* t_bwd, const uint8_t* packed,
@@ -1006,19 +996,12 @@ int fm_flow_loss_fused_bitmask(float* depth, const float* k, const float* kinv, 
   const float* pk = reinterpret_cast<const float*>(packed);
   fm_layout lay[5] = {};  // (only the depth stack is read beside the packed bytes)
   if (depth_layout) lay[0] = depth_layout[0];
-  const fm_layout* layouts = depth_layout && (lay[0].frame_stride != 0 || lay[0].batch_stride != 0) ? lay : nullptr;
-  if (exp_avg == nullptr) {
-    FM_CHECK_ARG(exp_avg_sq == nullptr && touched == nullptr);
-    return flow_loss_launch(depth, k, kinv, t_fwd, t_bwd, nullptr, nullptr, nullptr, nullptr, pk, scale, batch, frames, height, width, mapping_kind,
-                            delta, aspect_x, aspect_y, grad_depth, acc, items_per_thread, nullptr, layouts, stream, taps, true);
-  }
-  FM_CHECK_ARG(exp_avg_sq && touched && scale && grad_depth && step >= 1 && width % 4 == 0);
-  FM_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0);
-  auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  FM_CHECK_ARG(aligned(exp_avg) && aligned(exp_avg_sq));
-  const FlowAdam adam{exp_avg, exp_avg_sq, touched, adam_coefficients((double)step, lr, beta1, beta2, eps, 0.0)};
+  FlowAdam adam;  // (no exp_avg: no update in the pass)
+  if (exp_avg == nullptr) FM_CHECK_ARG(exp_avg_sq == nullptr && touched == nullptr);
+  else FM_CHECK_ARG(flow_adam_args(adam, exp_avg, exp_avg_sq, touched, scale, grad_depth, width, step, lr, beta1, beta2, eps));
   return flow_loss_launch(depth, k, kinv, t_fwd, t_bwd, nullptr, nullptr, nullptr, nullptr, pk, scale, batch, frames, height, width, mapping_kind,
-                          delta, aspect_x, aspect_y, grad_depth, acc, items_per_thread, &adam, layouts, stream, taps, true);
+                          delta, aspect_x, aspect_y, grad_depth, acc, items_per_thread, exp_avg ? &adam : nullptr, layout_is_view(depth_layout) ? lay : nullptr,
+                          stream, taps, true);
 }
 
 int fm_flow_loss_finalize(double* acc, const float* k, const float* kinv, const float* t_fwd, const float* t_bwd,
@@ -1030,21 +1013,21 @@ int fm_flow_loss_finalize(double* acc, const float* k, const float* kinv, const 
   FM_LAUNCH_STATUS();
 }
 
+// Workgroups per row of the two mask reductions (sum2_kernel, masks_binary_kernel): 4096 elements each, about 4096 workgroups in all at most.
+static inline long mask_reduce_blocks(long n, long rows) {
+  const long blocks = (n + 256 * 16 - 1) / (256 * 16), cap = 4096 / rows + 1;
+  return blocks > cap ? cap : blocks;
+}
+
 static int valid_norm_launch(const float* mask_fwd, const float* mask_bwd, int batch, int frames_per_batch, long n, float weight, double* vsum,
                              float* norm, const fm_layout* layouts, void* stream) {
   FM_CHECK_ARG(mask_fwd && vsum && norm && batch >= 0 && frames_per_batch >= 0 && n >= 0 && (long)batch * frames_per_batch <= 65535);
   hipStream_t st = (hipStream_t)stream;
   long fs[2], bs[2];
-  for (int i = 0; i < 2; ++i) {
-    const bool given = layouts && (layouts[i].frame_stride != 0 || layouts[i].batch_stride != 0);
-    fs[i] = given ? layouts[i].frame_stride : n;
-    bs[i] = given ? layouts[i].batch_stride : n * frames_per_batch;
-  }
+  for (int i = 0; i < 2; ++i) layout_strides(layouts, i, n, frames_per_batch, fs[i], bs[i]);  // (taken as they are: nothing is asked of them)
   if (hipMemsetAsync(vsum, 0, sizeof(double), st) != hipSuccess) return FM_ERR_LAUNCH;
   if (n > 0 && batch * frames_per_batch > 0) {
-    long blocks = (n + 256 * 16 - 1) / (256 * 16);
-    const long cap = 4096 / ((long)batch * frames_per_batch) + 1;
-    if (blocks > cap) blocks = cap;
+    const long blocks = mask_reduce_blocks(n, (long)batch * frames_per_batch);
     hipLaunchKernelGGL(sum2_kernel, dim3((unsigned)blocks, (unsigned)(batch * frames_per_batch)), dim3(256), 0, st, mask_fwd, mask_bwd, n, frames_per_batch,
                        fs[0], bs[0], fs[1], bs[1], vsum);
   }
@@ -1071,15 +1054,12 @@ static int pack_launch(const float* flow_fwd, const float* flow_bwd, const float
   if (packed_bits) packed = reinterpret_cast<float*>(packed_bits);
   FM_CHECK_ARG(flow_fwd && flow_bwd && mask_fwd && mask_bwd && packed);
   FM_CHECK_ARG(batch >= 1 && frames >= 2 && height >= 1 && width >= 1 && width % 4 == 0 && (long)batch * frames <= 65535);
-  auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   FM_CHECK_ARG(aligned(flow_fwd) && aligned(flow_bwd) && aligned(mask_fwd) && aligned(mask_bwd) && aligned(packed));
   const int n = height * width, quads = n / 4;
   PackLayouts lay;
   const long per_frame[4] = {2L * n, 2L * n, n, n};
   for (int i = 0; i < 4; ++i) {
-    const bool given = layouts && (layouts[i].frame_stride != 0 || layouts[i].batch_stride != 0);
-    lay.fs[i] = given ? layouts[i].frame_stride : per_frame[i];
-    lay.bs[i] = given ? layouts[i].batch_stride : per_frame[i] * (frames - 1);
+    layout_strides(layouts, i, per_frame[i], frames - 1, lay.fs[i], lay.bs[i]);
     FM_CHECK_ARG(lay.fs[i] >= per_frame[i] && lay.fs[i] % 4 == 0 && lay.bs[i] % 4 == 0);
   }
   int bx = (quads + 255) / 256;
@@ -1121,15 +1101,11 @@ int fm_flow_masks_binary(const float* mask_fwd, const float* mask_bwd, int batch
   hipStream_t st = (hipStream_t)stream;
   long fs[2], bs[2];
   for (int i = 0; i < 2; ++i) {
-    const bool given = layouts && (layouts[i].frame_stride != 0 || layouts[i].batch_stride != 0);
-    fs[i] = given ? layouts[i].frame_stride : pixels;
-    bs[i] = given ? layouts[i].batch_stride : pixels * pairs;
+    layout_strides(layouts, i, pixels, pairs, fs[i], bs[i]);
     FM_CHECK_ARG(fs[i] >= pixels);
   }
   if (hipMemsetAsync(not_binary, 0, sizeof(int), st) != hipSuccess) return FM_ERR_LAUNCH;
-  long blocks = (pixels + 256 * 16 - 1) / (256 * 16);
-  const long cap = 4096 / ((long)batch * pairs) + 1;
-  if (blocks > cap) blocks = cap;
+  const long blocks = mask_reduce_blocks(pixels, (long)batch * pairs);
   hipLaunchKernelGGL(masks_binary_kernel, dim3((unsigned)blocks, (unsigned)(batch * pairs)), dim3(256), 0, st, mask_fwd, mask_bwd, pixels, pairs, fs[0],
                      bs[0], fs[1], bs[1], not_binary);
   FM_LAUNCH_STATUS();

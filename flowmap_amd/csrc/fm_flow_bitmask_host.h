@@ -11,19 +11,21 @@
 #include <vector>
 
 #include "../../include/flowmap_hip.h"
+#include "fm_residual_args.h"
 
 namespace fm {
 namespace bitmask_host {
 
-// a (batch, frames, per_frame) stack read through an fm_layout ({0, 0} / NULL = dense) into a dense vector
+// a (batch, frames, per_frame) stack read through an fm_layout ({0, 0} / NULL = dense) into a dense vector: how the host builds of the
+// `_views` entry points (here and in tests/host_sim) read a frame window
 inline std::vector<float> densify(const float* p, const fm_layout* lay, int batch, int frames, size_t per_frame) {
   std::vector<float> out;
   if (!p) return out;
-  const bool given = lay && (lay->frame_stride != 0 || lay->batch_stride != 0);
-  const size_t fs = given ? (size_t)lay->frame_stride : per_frame, bs = given ? (size_t)lay->batch_stride : per_frame * frames;
+  long fs, bs;
+  layout_strides(lay, 0, (long)per_frame, frames, fs, bs);
   out.resize((size_t)batch * frames * per_frame);
   for (int b = 0; b < batch; ++b)
-    for (int f = 0; f < frames; ++f) std::memcpy(out.data() + ((size_t)b * frames + f) * per_frame, p + b * bs + f * fs, per_frame * sizeof(float));
+    for (int f = 0; f < frames; ++f) std::memcpy(out.data() + ((size_t)b * frames + f) * per_frame, p + (size_t)b * bs + (size_t)f * fs, per_frame * sizeof(float));
   return out;
 }
 
@@ -91,7 +93,7 @@ int fm_flow_loss_fused_bitmask(float* depth, const float* k, const float* kinv, 
                                float* grad_depth, double* acc, int items, const fm_layout* depth_layout, const fm_flow_taps* taps, float* exp_avg,
                                float* exp_avg_sq, const uint8_t* touched, long step, double lr, double beta1, double beta2, double eps, void* stream) {
   if (!packed || !depth || !k || !kinv || !acc || batch < 1 || frames < 2 || height < 1 || width < 1 || width % 4 != 0) return 1;
-  const bool view = depth_layout && (depth_layout->frame_stride != 0 || depth_layout->batch_stride != 0);
+  const bool view = fm::layout_is_view(depth_layout);
   if (view && (taps || exp_avg)) return 1;
   const size_t n = (size_t)height * width, quads = n / 4, chunks = (quads + 63) / 64, stride = FM_FLOW_BITMASK_CHUNK_BYTES;
   std::vector<float> wide((size_t)batch * frames * chunks * 6 * 64 * 4, 0.f);  // the fp32 packed layout of the same inputs

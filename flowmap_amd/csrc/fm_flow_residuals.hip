@@ -172,11 +172,10 @@ int fm_flow_residuals(const float* depth, const float* k, const float* kinv, con
   ResidualParams p{depth, k, kinv, t_fwd, t_bwd, flow_fwd, flow_bwd, sums ? mask_fwd : nullptr, sums ? mask_bwd : nullptr, residual_fwd, residual_bwd,
                    pred_fwd, pred_bwd, workspace};
   const long n = (long)height * width;
-  FM_CHECK_ARG(flow_residual_strides(layouts, batch, frames, n, p.fs, p.bs));
+  FM_CHECK_ARG(flow_strides(layouts, batch, frames, n, p.fs, p.bs));
   p.frames = frames, p.height = height, p.width = width, p.first_pair = first_pair, p.count = count;
   p.blocks = (int)flow_residual_blocks(n);
   p.delta = delta, p.ax = aspect_x, p.ay = aspect_y;
-  auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   bool vec4 = width % 4 == 0 && aligned(depth) && aligned(flow_fwd) && aligned(flow_bwd) && aligned(residual_fwd) && aligned(residual_bwd);
   vec4 = vec4 && (!sums || (aligned(mask_fwd) && aligned(mask_bwd))) && (!pred_fwd || (aligned(pred_fwd) && aligned(pred_bwd)));
   for (int i = 0; i < (sums ? 5 : 3); ++i) vec4 = vec4 && p.fs[i] % 4 == 0 && p.bs[i] % 4 == 0;

@@ -87,7 +87,7 @@ int fm_flow_residuals(const float* depth, const float* k, const float* kinv, con
     return 1;
   const bool sums = pair_sum != nullptr;
   long fs[5], bs[5];
-  if (!fm::flow_residual_strides(layouts, batch, frames, (long)height * width, fs, bs)) return 1;
+  if (!fm::flow_strides(layouts, batch, frames, (long)height * width, fs, bs)) return 1;
   const float* const flow[2] = {flow_fwd, flow_bwd};
   const float* const mask[2] = {sums ? mask_fwd : nullptr, sums ? mask_bwd : nullptr};
   float* const res[2] = {residual_fwd, residual_bwd};

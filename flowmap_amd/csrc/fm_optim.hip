@@ -123,10 +123,9 @@ extern "C" {
 int fm_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long count, long step, double lr, double beta1,
                  double beta2, double eps, double weight_decay, void* stream) {
   FM_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && count >= 0 && step >= 1);
-  FM_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && (float)eps > 0.f);  // eps: see the header of this file
+  FM_CHECK_ARG(adam_betas_ok(beta1, beta2) && (float)eps > 0.f);  // eps: see the header of this file
   if (count == 0) return FM_OK;
   const AdamCoef c = adam_coefficients((double)step, lr, beta1, beta2, eps, weight_decay);
-  auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   const int vec_ok = aligned(param) && aligned(grad) && aligned(exp_avg) && aligned(exp_avg_sq);
   long blocks = (count / 4 + 255) / 256;
   if (blocks < 1) blocks = 1;
@@ -139,9 +138,8 @@ int fm_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
 int fm_adam_step_capturable(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long count, const float* step,
                             double lr, double beta1, double beta2, double eps, double weight_decay, void* stream) {
   FM_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && step && count >= 0);
-  FM_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && (float)eps > 0.f);  // eps: see the header of this file
+  FM_CHECK_ARG(adam_betas_ok(beta1, beta2) && (float)eps > 0.f);  // eps: see the header of this file
   if (count == 0) return FM_OK;
-  auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   const int vec_ok = aligned(param) && aligned(grad) && aligned(exp_avg) && aligned(exp_avg_sq);
   long blocks = (count / 4 + 255) / 256;
   if (blocks < 1) blocks = 1;
@@ -154,7 +152,7 @@ int fm_adam_step_capturable(float* param, const float* grad, float* exp_avg, flo
 int fm_adam_step_elements(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const int64_t* elements, long count, long step,
                           double lr, double beta1, double beta2, double eps, double weight_decay, void* stream) {
   FM_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && count >= 0 && step >= 1 && (elements || count == 0));
-  FM_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && (float)eps > 0.f);  // eps: see the header of this file
+  FM_CHECK_ARG(adam_betas_ok(beta1, beta2) && (float)eps > 0.f);  // eps: see the header of this file
   if (count == 0) return FM_OK;
   const AdamCoef c = adam_coefficients((double)step, lr, beta1, beta2, eps, weight_decay);
   hipLaunchKernelGGL(adam_elements_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,

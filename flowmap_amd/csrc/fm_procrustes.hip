@@ -22,6 +22,7 @@
 #include "../../include/flowmap_hip.h"
 #include "fm_device.h"
 #include "fm_pose.h"
+#include "fm_residual_args.h"
 
 namespace fm {
 
@@ -2011,22 +2012,11 @@ static inline bool proc_layouts(ProcParams& p, const fm_layout* layouts, int fra
   const long n = (long)height * width;
   const long per_frame[4] = {n, 3 * n, 2 * n, n};
   const long frames_of[4] = {frames, frames, frames - 1, frames - 1};
-  bool any = false;
   for (int i = 0; i < 4; ++i) {
-    const bool given = layouts && (layouts[i].frame_stride != 0 || layouts[i].batch_stride != 0);
-    any = any || given;
-    p.fs[i] = given ? layouts[i].frame_stride : per_frame[i];
-    p.bs[i] = given ? layouts[i].batch_stride : per_frame[i] * frames_of[i];
+    layout_strides(layouts, i, per_frame[i], frames_of[i], p.fs[i], p.bs[i]);
     if (p.fs[i] < per_frame[i]) return false;
   }
-  (void)any;
   return true;
-}
-static inline bool proc_is_view(const fm_layout* layouts) {
-  if (!layouts) return false;
-  for (int i = 0; i < 4; ++i)
-    if (layouts[i].frame_stride != 0 || layouts[i].batch_stride != 0) return true;
-  return false;
 }
 
 static inline int choose_iters(long points) {
@@ -2053,7 +2043,7 @@ static int procrustes_stats_launch(const float* depth, const float* kinv, const 
   dim3 grid((unsigned)((points + 256L * iters - 1) / (256L * iters)), (unsigned)pairs);
   const dim3 fgrid((unsigned)((pairs + 63) / 64));
   const bool dense = dense_tiled(depth, surfaces, indices, points, batch_repeat, height, width, pairs);
-  FM_CHECK_ARG(!(dense && proc_is_view(layouts)));  // the tiled dense kernels read dense stacks
+  FM_CHECK_ARG(!(dense && layout_is_view(layouts, 4)));  // the tiled dense kernels read dense stacks
   if (hipMemsetAsync(stats, 0, sizeof(double) * (size_t)pairs * kStatStride, st) != hipSuccess) return FM_ERR_LAUNCH;
   if (dense) {
     const long total = dense_blocks(height, width, pairs);
@@ -2197,7 +2187,7 @@ static int scatter_launch(const float* depth, const float* kinv, const float* su
   p.weight_sens = weight_sensitivity;
   p.batch_repeat = batch_repeat;
   FM_CHECK_ARG(proc_layouts(p, layouts, frames, height, width));
-  FM_CHECK_ARG(!(proc_is_view(layouts) && batch_repeat > 1));
+  FM_CHECK_ARG(!(layout_is_view(layouts, 4) && batch_repeat > 1));
   const int iters = choose_iters(points);
   dim3 grid((unsigned)((points + 256L * iters - 1) / (256L * iters)), (unsigned)pairs);
   if (batch_repeat > 1 && !surfaces) {
@@ -2314,8 +2304,8 @@ static int scatter_plan_launch(const float* bwd_flow, const int64_t* indices, lo
   FM_CHECK_ARG(bwd_flow && keys && weights && points >= 1 && batch >= 1 && frames >= 2 && height >= 1 && width >= 1);
   FM_CHECK_ARG((long)height * width < (1L << 30) && (long)batch * (frames - 1) <= 65535);
   const long n2 = 2L * height * width;
-  const bool given = flow_layout && (flow_layout->frame_stride != 0 || flow_layout->batch_stride != 0);
-  const long fs = given ? flow_layout->frame_stride : n2, bs = given ? flow_layout->batch_stride : n2 * (frames - 1);
+  long fs, bs;
+  layout_strides(flow_layout, 0, n2, frames - 1, fs, bs);
   FM_CHECK_ARG(fs >= n2);
   hipLaunchKernelGGL(procrustes_scatter_plan_kernel, dim3((unsigned)((points + 255) / 256), (unsigned)(batch * (frames - 1))), dim3(256), 0,
                      (hipStream_t)stream, bwd_flow, indices, points, frames, height, width, keys, weights, fs, bs);

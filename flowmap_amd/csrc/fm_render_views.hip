@@ -159,7 +159,6 @@ int fm_render_views(const float* depth, const float* kinv, const float* ext, con
                     float near, float background, float* color, float* out_depth, int32_t* source, void* workspace, void* stream) {
   FM_CHECK_ARG(render_views_args_ok(depth, kinv, ext, colors, view_k, view_ext, pairs, n_pairs, batch, frames, height, width, views, out_height, out_width,
                                     radius, near, background, color, out_depth, source, workspace));
-  auto aligned = [](const void* q, uintptr_t to) { return (reinterpret_cast<uintptr_t>(q) & (to - 1)) == 0; };
   FM_CHECK_ARG(aligned(workspace, 8));
   const long n = (long)height * width, out_pixels = (long)out_height * out_width;
   const long key_bytes = render_views_key_bytes(batch, views, out_pixels);

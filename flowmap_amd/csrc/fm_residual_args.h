@@ -1,5 +1,5 @@
 // Argument checks and size formulas of the residual entry points (include/flowmap_hip.h: fm_flow_residuals, fm_track_residuals,
-// fm_alignment_residuals, fm_focal_sweep, fm_depth_consistency, fm_render_views, fm_voxel_cloud, fm_tsdf_volume, fm_tsdf_surface_count / _emit and their size functions), stated ONCE: the device build (fm_*.hip) and the serial host build of
+// fm_alignment_residuals, fm_focal_sweep, fm_depth_consistency, fm_render_views, fm_voxel_cloud, fm_tsdf_volume, fm_tsdf_surface_count / _emit and their size functions) and the fm_layout rules of the `_views` entry points, stated ONCE: the device build (fm_*.hip) and the serial host build of
 // the same ABI (fm_*_host.h) both call these, so the two refuse the same calls and size the same workspaces.  Plain C++, no HIP.
 // Device-only, and therefore not here: the 16-byte path's eligibility and the pointer alignment the kernels need (the host build reads
 // element by element and never touches the workspace).
@@ -23,6 +23,41 @@ static inline bool res_window_ok(int batch, int frames, int first_pair, int coun
   return batch >= 1 && frames >= 2 && first_pair >= 0 && count >= 1 && (long)first_pair + count <= frames - 1 && (long)batch * count <= kResMaxRows;
 }
 
+// ---- fm_layout: the element strides of a frame window read in place ----
+// Every `_views` launcher of the device build (fm_flow.hip, fm_procrustes.hip, fm_flow_residuals.hip) and the host build's reader (densify,
+// fm_flow_bitmask_host.h) resolve a layout here.  What a launcher asks of the strides beyond this — divisible by 4 for a 16-byte path, frames
+// apart only, or nothing — is its own and stays with it.
+// layout_is_view: does any of the `n` entries at `layouts` describe a view?  NULL and {0, 0} both mean dense.
+static inline bool layout_is_view(const fm_layout* layouts, int n = 1) {
+  for (int i = 0; layouts && i < n; ++i)
+    if (layouts[i].frame_stride != 0 || layouts[i].batch_stride != 0) return true;
+  return false;
+}
+
+// Element strides of stack i: `per_frame` elements per frame, `frames_of` frames per batch entry when dense.
+static inline void layout_strides(const fm_layout* layouts, int i, long per_frame, long frames_of, long& fs, long& bs) {
+  const bool view = layouts && layout_is_view(layouts + i);
+  fs = view ? layouts[i].frame_stride : per_frame;
+  bs = view ? layouts[i].batch_stride : per_frame * frames_of;
+}
+
+// Frames do not overlap, and neither do batch entries (a batch-expanded stack, stride 0 over the batch, is the caller's to copy).
+static inline bool layout_apart(long fs, long bs, long per_frame, long frames_of, int batch) {
+  return fs >= per_frame && (batch == 1 || bs >= fs * (frames_of - 1) + per_frame);
+}
+
+// The five stacks of the flow loss — depth, flow_fwd, flow_bwd, mask_fwd, mask_bwd — for the fused pass and the residual maps alike;
+// false: a stack's frames or batch entries would overlap.
+static inline bool flow_strides(const fm_layout* layouts, int batch, int frames, long pixels, long fs[5], long bs[5]) {
+  const long per_frame[5] = {pixels, 2 * pixels, 2 * pixels, pixels, pixels};
+  const long frames_of[5] = {frames, frames - 1, frames - 1, frames - 1, frames - 1};
+  for (int i = 0; i < 5; ++i) {
+    layout_strides(layouts, i, per_frame[i], frames_of[i], fs[i], bs[i]);
+    if (!layout_apart(fs[i], bs[i], per_frame[i], frames_of[i], batch)) return false;
+  }
+  return true;
+}
+
 // ---- flow ----
 static inline long flow_residual_blocks(long pixels) { return (pixels + kFlowResTile - 1) / kFlowResTile; }
 static inline bool flow_residual_blocks_args_ok(int height, int width, const int* blocks) { return blocks && res_frame_ok(height, width); }
@@ -38,20 +73,6 @@ static inline bool flow_residuals_args_ok(const float* depth, const float* k, co
   if ((pair_valid != nullptr) != sums || (workspace != nullptr) != sums || (sums && !(mask_fwd && mask_bwd))) return false;
   if (!res_frame_ok(height, width) || !res_window_ok(batch, frames, first_pair, count)) return false;
   return mapping_kind >= 0 && mapping_kind <= 2 && aspect_x > 0.f && aspect_y > 0.f;
-}
-
-// Element strides of depth, flow_fwd, flow_bwd, mask_fwd, mask_bwd (dense unless the caller described a view); false: a stack's frames or
-// batch entries would overlap.
-static inline bool flow_residual_strides(const fm_layout* layouts, int batch, int frames, long pixels, long fs[5], long bs[5]) {
-  const long per_frame[5] = {pixels, 2 * pixels, 2 * pixels, pixels, pixels};
-  const long frames_of[5] = {frames, frames - 1, frames - 1, frames - 1, frames - 1};
-  for (int i = 0; i < 5; ++i) {
-    const bool given = layouts && (layouts[i].frame_stride != 0 || layouts[i].batch_stride != 0);
-    fs[i] = given ? layouts[i].frame_stride : per_frame[i];
-    bs[i] = given ? layouts[i].batch_stride : per_frame[i] * frames_of[i];
-    if (fs[i] < per_frame[i] || (batch != 1 && bs[i] < fs[i] * (frames_of[i] - 1) + per_frame[i])) return false;
-  }
-  return true;
 }
 
 // ---- tracking ----
@@ -138,6 +159,14 @@ constexpr int kRenderTile = 1024;        // source pixels per workgroup of rende
 constexpr int kRenderMaxRadius = 2;      // a splat covers (2r+1)² target pixels
 constexpr long kRenderMaxSources = 1L << 31;  // `source` is int32: frames x height x width stays below this
 static inline long render_blocks(long pixels) { return (pixels + kRenderTile - 1) / kRenderTile; }
+// a (frames, height, width) stack of depth maps whose pixels an int32 can name (render_views' `source`) ...
+static inline bool depth_sources_ok(int frames, int height, int width) {
+  return frames >= 1 && res_frame_ok(height, width) && (long)frames * height * width < kRenderMaxSources;
+}
+// ... and whose frames are a grid dimension as well (voxel cloud, TSDF)
+static inline bool depth_stack_ok(int frames, int height, int width) { return frames <= kResMaxRows && depth_sources_ok(frames, height, width); }
+// colours in <=> colours out
+static inline bool color_pair_ok(const void* colors_in, const void* colors_out) { return (colors_in != nullptr) == (colors_out != nullptr); }
 // bytes of workspace: the (B,V,OH,OW) 64-bit z-buffer, then one 16-float pose row per (batch entry, pair)
 static inline long render_views_key_bytes(long batch, long views, long out_pixels) { return 8 * batch * views * out_pixels; }
 static inline long render_views_workspace_bytes(long batch, long views, long out_pixels, long n_pairs) {
@@ -157,9 +186,9 @@ static inline bool render_views_args_ok(const float* depth, const float* kinv, c
                                         int out_height, int out_width, int radius, float near, float background, const float* color, const float* out_depth,
                                         const int32_t* source, const void* workspace) {
   if (!(depth && kinv && ext && view_k && view_ext && out_depth && source && workspace)) return false;
-  if ((colors != nullptr) != (color != nullptr)) return false;
+  if (!color_pair_ok(colors, color)) return false;
   if (!render_views_shape_ok(batch, views, out_height, out_width, n_pairs) || (n_pairs > 0 && !pairs)) return false;
-  if (!(frames >= 1 && res_frame_ok(height, width) && (long)frames * height * width < kRenderMaxSources)) return false;
+  if (!depth_sources_ok(frames, height, width)) return false;
   if (radius < 0 || radius > kRenderMaxRadius) return false;
   return near >= 0.f && near < __builtin_inff() && background == background;
 }
@@ -184,8 +213,7 @@ static inline bool voxel_cloud_args_ok(const float* depth, const float* kinv, co
                                        const unsigned long long* counters, const void* workspace) {
   (void)keep, (void)pixel_slot;  // (optional)
   if (!(depth && kinv && ext && xyz && count && first && slot && counters && workspace)) return false;
-  if ((colors != nullptr) != (rgb != nullptr)) return false;
-  if (!(frames >= 1 && frames <= kResMaxRows && res_frame_ok(height, width) && (long)frames * height * width < kRenderMaxSources)) return false;
+  if (!color_pair_ok(colors, rgb) || !depth_stack_ok(frames, height, width)) return false;
   const float inv = (float)(1.0 / voxel_size);  // (finite and normal, or the call is refused)
   if (!(voxel_size > 0.0 && voxel_size < (double)__builtin_inff() && inv >= 1.17549435e-38f && inv < __builtin_inff())) return false;
   if (min_count < 1 || capacity < 1 || capacity > kVoxelMaxCapacity) return false;
@@ -212,8 +240,7 @@ static inline bool tsdf_volume_args_ok(const float* depth, const float* k, const
                                        const float* color, const int32_t* color_weight) {
   (void)keep;  // (optional)
   if (!(depth && k && ext && world_to_camera && tsdf && weight)) return false;
-  if ((colors != nullptr) != (color != nullptr) || (colors != nullptr) != (color_weight != nullptr)) return false;
-  if (!(frames >= 1 && frames <= kResMaxRows && res_frame_ok(height, width) && (long)frames * height * width < kRenderMaxSources)) return false;
+  if (!color_pair_ok(colors, color) || !color_pair_ok(colors, color_weight) || !depth_stack_ok(frames, height, width)) return false;
   if (!(first_frame >= 0 && count >= 1 && (long)first_frame + count <= frames)) return false;
   if (!tsdf_dims_ok(nx, ny, nz) || !tsdf_grid_ok(ox, oy, oz, voxel_size)) return false;
   return truncation > 0.f && truncation < __builtin_inff() && near >= 0.f && near < __builtin_inff();

@@ -142,7 +142,7 @@ static ImageStack image_stack(const Tensor& t, const char* what) {
   }
   if (frames_dense && (t.size(1) == 1 || t.stride(1) >= per_frame)) {
     const int64_t frame_stride = t.size(1) == 1 ? per_frame : t.stride(1);
-    // batch entries must not overlap — the launchers (flow_loss_launch, pack_launch) refuse a batch stride below the extent of one entry, so
+    // batch entries must not overlap — the launchers (fm_residual_args.h: layout_apart) refuse a batch stride below the extent of one entry, so
     // a batch-EXPANDED stack (stride 0 over the batch) is copied here instead of failing there with "invalid argument"
     if (t.size(0) == 1 || t.stride(0) >= frame_stride * (t.size(1) - 1) + per_frame) {
       out.t = t;
@@ -1723,6 +1723,33 @@ static std::vector<Tensor> render_views_op(const Tensor& depth_in, const Tensor&
   return {color, out_depth, source};
 }
 
+// A (F,H,W) stack of depth maps with its per-frame camera matrices and the optional `colors` and `keep`, as voxel_cloud_op and
+// tsdf_volume_op take them: on one device, float32 (keep: bool), contiguous, shapes checked against the stack's limits (fm_residual_args.h:
+// depth_stack_ok).  `op` and `camera_name` (the (F,3,3) matrices: intrinsics for one, their inverses for the other) go into the messages.
+struct DepthStack {
+  c10::Device dev;
+  bool has_colors = false, has_keep = false;
+  Tensor depth, camera, ext, colors, keep;
+  int64_t f = 0, h = 0, w = 0;
+};
+static DepthStack depth_stack(const char* op, const Tensor& depth_in, const Tensor& camera_in, const char* camera_name, const Tensor& ext_in,
+                              const OptTensor& colors_in, const OptTensor& keep_in) {
+  const bool has_colors = colors_in.has_value() && colors_in->defined(), has_keep = keep_in.has_value() && keep_in->defined();
+  const Tensor colors_t = has_colors ? *colors_in : Tensor(), keep_t = has_keep ? *keep_in : Tensor();
+  DepthStack s{check_device({&depth_in, &camera_in, &ext_in, &colors_t, &keep_t}), has_colors, has_keep};
+  s.depth = f32c(depth_in.detach(), "depths"), s.camera = f32c(camera_in.detach(), camera_name), s.ext = f32c(ext_in.detach(), "extrinsics");
+  if (has_colors) s.colors = f32c(colors_t.detach(), "colors");
+  TORCH_CHECK(s.depth.dim() == 3, "flowmap_amd: depths must be (frame, height, width)");
+  const int64_t f = s.f = s.depth.size(0), h = s.h = s.depth.size(1), w = s.w = s.depth.size(2);
+  TORCH_CHECK(f >= 1 && f <= 65535 && h * w >= 1 && h * w < (int64_t(1) << 30) && f * h * w < (int64_t(1) << 31), "flowmap_amd: ", op,
+              " indexes pixels with int32 and takes at most 65 535 frames per call (got ", f, " x ", h, " x ", w, ")");
+  TORCH_CHECK(s.camera.sizes() == at::IntArrayRef({f, 3, 3}) && s.ext.sizes() == at::IntArrayRef({f, 4, 4}), "flowmap_amd: intrinsics / extrinsics do not match the depths");
+  TORCH_CHECK(!has_colors || s.colors.sizes() == at::IntArrayRef({f, 3, h, w}), "flowmap_amd: colors must be (frame, 3, height, width)");
+  TORCH_CHECK(!has_keep || (keep_t.scalar_type() == at::kBool && keep_t.sizes() == s.depth.sizes()), "flowmap_amd: keep must be a bool tensor shaped like the depths");
+  if (has_keep) s.keep = keep_t.contiguous();
+  return s;
+}
+
 // export.voxel_point_cloud (fm_voxel_cloud): the world points of the depth maps merged per cell of a world-space grid in one pass over
 // depth.  Not differentiable.  -> {xyz, rgb (empty without colors), count, first, slot: `capacity` rows each, written up to the rows
 // drawn and in no particular order; pixel_slot (F,H,W; empty without details); counters (8 int64 on the device)}.  The hash table is
@@ -1730,19 +1757,7 @@ static std::vector<Tensor> render_views_op(const Tensor& depth_in, const Tensor&
 static std::vector<Tensor> voxel_cloud_op(const Tensor& depth_in, const Tensor& kinv_in, const Tensor& ext_in, const OptTensor& colors_in, const OptTensor& keep_in,
                                           double voxel_size, int64_t min_count, int64_t capacity, bool details) {
   at::NoGradGuard no_grad;
-  const bool has_colors = colors_in.has_value() && colors_in->defined(), has_keep = keep_in.has_value() && keep_in->defined();
-  const Tensor colors_t = has_colors ? *colors_in : Tensor(), keep_t = has_keep ? *keep_in : Tensor();
-  const auto dev = check_device({&depth_in, &kinv_in, &ext_in, &colors_t, &keep_t});
-  const Tensor depth = f32c(depth_in.detach(), "depths"), kinv = f32c(kinv_in.detach(), "inverse intrinsics"), ext = f32c(ext_in.detach(), "extrinsics");
-  const Tensor colors = has_colors ? f32c(colors_t.detach(), "colors") : Tensor();
-  TORCH_CHECK(depth.dim() == 3, "flowmap_amd: depths must be (frame, height, width)");
-  const int64_t f = depth.size(0), h = depth.size(1), w = depth.size(2);
-  TORCH_CHECK(f >= 1 && f <= 65535 && h * w >= 1 && h * w < (int64_t(1) << 30) && f * h * w < (int64_t(1) << 31),
-              "flowmap_amd: voxel_point_cloud indexes pixels with int32 and takes at most 65 535 frames per call (got ", f, " x ", h, " x ", w, ")");
-  TORCH_CHECK(kinv.sizes() == at::IntArrayRef({f, 3, 3}) && ext.sizes() == at::IntArrayRef({f, 4, 4}), "flowmap_amd: intrinsics / extrinsics do not match the depths");
-  TORCH_CHECK(!has_colors || colors.sizes() == at::IntArrayRef({f, 3, h, w}), "flowmap_amd: colors must be (frame, 3, height, width)");
-  TORCH_CHECK(!has_keep || (keep_t.scalar_type() == at::kBool && keep_t.sizes() == depth.sizes()), "flowmap_amd: keep must be a bool tensor shaped like the depths");
-  const Tensor keep = has_keep ? keep_t.contiguous() : Tensor();
+  const auto [dev, has_colors, has_keep, depth, kinv, ext, colors, keep, f, h, w] = depth_stack("voxel_point_cloud", depth_in, kinv_in, "inverse intrinsics", ext_in, colors_in, keep_in);
   TORCH_CHECK(capacity >= 1 && capacity <= (int64_t(1) << 28), "flowmap_amd: voxel_point_cloud: capacity must be in [1, 2^28] (got ", capacity, ")");
   long slots = 0, bytes = 0;
   FM_CALL(fm_voxel_cloud_workspace, (long)capacity, &slots, &bytes);
@@ -1766,19 +1781,7 @@ static std::vector<Tensor> tsdf_volume_op(const Tensor& depth_in, const Tensor& 
                                           int64_t first_frame, int64_t count, double ox, double oy, double oz, int64_t nx, int64_t ny, int64_t nz,
                                           double voxel_size, double truncation, double near) {
   at::NoGradGuard no_grad;
-  const bool has_colors = colors_in.has_value() && colors_in->defined(), has_keep = keep_in.has_value() && keep_in->defined();
-  const Tensor colors_t = has_colors ? *colors_in : Tensor(), keep_t = has_keep ? *keep_in : Tensor();
-  const auto dev = check_device({&depth_in, &k_in, &ext_in, &colors_t, &keep_t});
-  const Tensor depth = f32c(depth_in.detach(), "depths"), k = f32c(k_in.detach(), "intrinsics"), ext = f32c(ext_in.detach(), "extrinsics");
-  const Tensor colors = has_colors ? f32c(colors_t.detach(), "colors") : Tensor();
-  TORCH_CHECK(depth.dim() == 3, "flowmap_amd: depths must be (frame, height, width)");
-  const int64_t f = depth.size(0), h = depth.size(1), w = depth.size(2);
-  TORCH_CHECK(f >= 1 && f <= 65535 && h * w >= 1 && h * w < (int64_t(1) << 30) && f * h * w < (int64_t(1) << 31),
-              "flowmap_amd: tsdf_volume indexes pixels with int32 and takes at most 65 535 frames per call (got ", f, " x ", h, " x ", w, ")");
-  TORCH_CHECK(k.sizes() == at::IntArrayRef({f, 3, 3}) && ext.sizes() == at::IntArrayRef({f, 4, 4}), "flowmap_amd: intrinsics / extrinsics do not match the depths");
-  TORCH_CHECK(!has_colors || colors.sizes() == at::IntArrayRef({f, 3, h, w}), "flowmap_amd: colors must be (frame, 3, height, width)");
-  TORCH_CHECK(!has_keep || (keep_t.scalar_type() == at::kBool && keep_t.sizes() == depth.sizes()), "flowmap_amd: keep must be a bool tensor shaped like the depths");
-  const Tensor keep = has_keep ? keep_t.contiguous() : Tensor();
+  const auto [dev, has_colors, has_keep, depth, k, ext, colors, keep, f, h, w] = depth_stack("tsdf_volume", depth_in, k_in, "intrinsics", ext_in, colors_in, keep_in);
   TORCH_CHECK(nx >= 1 && ny >= 1 && nz >= 1 && nx < (int64_t(1) << 31) && ny < (int64_t(1) << 31) && nz < (int64_t(1) << 31) && nx * ny < (int64_t(1) << 31) &&
                   nx * ny * nz < (int64_t(1) << 31),
               "flowmap_amd: tsdf_volume: dims must be >= 1 with nx * ny * nz < 2^31 (got ", nx, " x ", ny, " x ", nz, ")");

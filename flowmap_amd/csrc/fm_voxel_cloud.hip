@@ -177,7 +177,6 @@ int fm_voxel_cloud(const float* depth, const float* kinv, const float* ext, cons
                    int32_t* pixel_slot, unsigned long long* counters, void* workspace, void* stream) {
   FM_CHECK_ARG(voxel_cloud_args_ok(depth, kinv, ext, colors, keep, frames, height, width, voxel_size, min_count, capacity, xyz, rgb, count, first, slot,
                                    pixel_slot, counters, workspace));
-  auto aligned = [](const void* q, uintptr_t to) { return (reinterpret_cast<uintptr_t>(q) & (to - 1)) == 0; };
   const long n = (long)height * width, slots = voxel_cloud_slots(capacity);
   unsigned long long* records = static_cast<unsigned long long*>(workspace);  // (slots, 8), then the keys (slots)
   unsigned long long* keys = records + (size_t)slots * kVoxelRecord;

@@ -17,6 +17,7 @@ the reference.
 
 from __future__ import annotations
 
+import ctypes
 from pathlib import Path
 from typing import Optional, Tuple
 
@@ -50,6 +51,12 @@ def _check_cloud_arguments(depths, intrinsics, extrinsics, colors, keep) -> Tupl
         if keep.device != depths.device:
             raise RuntimeError(f"flowmap_amd: keep is on {keep.device}, the depths on {depths.device}")
     return f, h, w
+
+
+def _check_stack_fits(what: str, f: int, h: int, w: int) -> None:
+    """The stack limits of voxel_point_cloud and tsdf_volume (fm_residual_args.h: depth_stack_ok)."""
+    if f > 65535 or h * w >= 1 << 30 or f * h * w >= 1 << 31:
+        raise ValueError(f"flowmap_amd: {what}: frames x height x width = {f} x {h} x {w} does not fit (at most 65535 frames, int32 pixel indices)")
 
 
 def world_point_cloud(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, colors: Optional[Tensor] = None,
@@ -111,8 +118,7 @@ def voxel_point_cloud(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, co
         raise ValueError(f"flowmap_amd: voxel_point_cloud: capacity must be an integer in [1, 2^28] (got {capacity!r})")
     if not isinstance(details, bool):
         raise ValueError(f"flowmap_amd: voxel_point_cloud: details must be a bool (got {details!r})")
-    if f > 65535 or h * w >= 1 << 30 or f * h * w >= 1 << 31:
-        raise ValueError(f"flowmap_amd: voxel_point_cloud: frames x height x width = {f} x {h} x {w} does not fit (at most 65535 frames, int32 pixel indices)")
+    _check_stack_fits("voxel_point_cloud", f, h, w)
     with torch.no_grad():
         if capacity is None:  # (counting a mask's candidates waits for the device once more: pass capacity to avoid it)
             capacity = min(voxel_default_capacity(f * h * w if keep is None else int(keep.sum())), VOXEL_MAX_CAPACITY)
@@ -127,10 +133,9 @@ def voxel_point_cloud(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, co
         rgb = None if colors is None else rgb[:rows][order]
         voxel_of = None
         if details:
-            slots = 2
-            while slots < 2 * capacity:
-                slots *= 2
-            row_of_slot = torch.full((slots + 1,), -1, dtype=torch.int32, device=depths.device)  # (the last entry serves pixel_slot == −1)
+            slots, table_bytes = ctypes.c_long(0), ctypes.c_long(0)
+            call("fm_voxel_cloud_workspace", capacity, ctypes.byref(slots), ctypes.byref(table_bytes))  # (the table's size, stated by the library)
+            row_of_slot = torch.full((slots.value + 1,), -1, dtype=torch.int32, device=depths.device)  # (the last entry serves pixel_slot == −1)
             row_of_slot[slot.long()] = torch.arange(rows, dtype=torch.int32, device=depths.device)
             voxel_of = row_of_slot[pixel_slot.long()]
     return VoxelCloud(xyz, rgb, count, first, {"masked": masked, "invalid": invalid, "out_of_range": out_of_range}, voxel_of, float(voxel_size))
@@ -200,8 +205,7 @@ def tsdf_volume(depths: Tensor, intrinsics: Tensor, extrinsics: Tensor, colors: 
     dims = tuple(int(v) for v in dims)
     if min(dims) < 1 or dims[0] * dims[1] * dims[2] >= TSDF_MAX_VOXELS:
         raise ValueError(f"flowmap_amd: {what}: dims must each be >= 1 with nx * ny * nz < 2^31 (got {dims!r})")
-    if f > 65535 or h * w >= 1 << 30 or f * h * w >= 1 << 31:
-        raise ValueError(f"flowmap_amd: {what}: frames x height x width = {f} x {h} x {w} does not fit (at most 65535 frames, int32 pixel indices)")
+    _check_stack_fits(what, f, h, w)
     first, count = parse_window(frames, f, what, "frames")
     with torch.no_grad():
         w2c, tsdf, weight, color, color_weight = _ops.tsdf_volume(depths, _ops._f32c(intrinsics.detach(), "intrinsics"), extrinsics, colors, keep, first, count,

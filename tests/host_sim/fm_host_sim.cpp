@@ -1669,16 +1669,7 @@ int fm_procrustes_bwd_planned(const float* corr, const float* kinv, float sens, 
 
 // ---- frame windows (fm_layout): the double gathers every view into a dense temporary and runs its dense namesake — the
 // semantics of the strides, none of the device kernels' pointer arithmetic ----
-static std::vector<float> sim_densify(const float* p, const fm_layout* lay, int batch, int frames, size_t per_frame) {
-  std::vector<float> out;
-  if (!p) return out;
-  const bool given = lay && (lay->frame_stride != 0 || lay->batch_stride != 0);
-  const size_t fs = given ? (size_t)lay->frame_stride : per_frame, bs = given ? (size_t)lay->batch_stride : per_frame * frames;
-  out.resize((size_t)batch * frames * per_frame);
-  for (int b = 0; b < batch; ++b)
-    for (int f = 0; f < frames; ++f) std::memcpy(out.data() + ((size_t)b * frames + f) * per_frame, p + b * bs + f * fs, per_frame * sizeof(float));
-  return out;
-}
+static const auto sim_densify = bitmask_host::densify;  // (fm_flow_bitmask_host.h: the one reader of an fm_layout on the host)
 static const float* sim_or_null(const std::vector<float>& v) { return v.empty() ? nullptr : v.data(); }
 
 int fm_flow_loss_fused_views(const float* depth, const float* k, const float* kinv, const float* t_fwd, const float* t_bwd,

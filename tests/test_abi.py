@@ -180,6 +180,105 @@ def test_residual_size_functions_at_the_tile_edges(both_builds):
     assert doubles.value == 2 * (5 * 5 * 2 + 5 * 65)
 
 
+# ---- fm_layout and the in-pass Adam arguments: calls the launchers refuse ---------------------------------------------------------------
+# Each call starts from one the device build would accept (never made: B = 2, F = 3, 8 x 16, every pointer the same 64-byte-aligned host
+# address) and breaks one thing.  Every check precedes the first HIP call, so the answer is FM_ERR_ARG (1) with or without a GPU; a call
+# that slipped past the checks would come back as 2 (launch failure) on a machine without one.
+
+N = 8 * 16
+VIEW_VALID = dict(batch=2, frames=3, height=8, width=16, mapping_kind=0, delta=0.01, aspect_x=1.0, aspect_y=1.0, items_per_thread=0, pairs=2, pixels=N,
+                  points=64, weight_sensitivity=0.0, weight=1.0, first_pair=0, count=2, step=1, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8)
+FLOW5 = [(N, 3), (2 * N, 2), (2 * N, 2), (N, 2), (N, 2)]  # (elements per frame, frames per batch entry) of depth, flow_fwd, flow_bwd, mask_fwd, mask_bwd
+PACK4 = [(2 * N, 2), (2 * N, 2), (N, 2), (N, 2)]  # flow_fwd, flow_bwd, mask_fwd, mask_bwd
+PROC4 = [(N, 3), (3 * N, 3), (2 * N, 2), (N, 2)]  # depth, surfaces, bwd_flow, weights
+NO_ADAM = {"taps", "exp_avg", "exp_avg_sq", "touched"}
+# label: (entry, its fm_layout parameter, the stacks that describes, parameters left NULL, batch entries must not overlap?, stacks whose
+#         strides must be divisible by 4, what makes a call with a dense layout invalid, builds)
+VIEW_ENTRIES = {
+    "flow": ("fm_flow_loss_fused_views", "layouts", FLOW5, {"packed"}, True, [], dict(batch=0), ("device build",)),
+    "flow-packed": ("fm_flow_loss_fused_views", "layouts", FLOW5, {"flow_fwd", "flow_bwd", "mask_fwd", "mask_bwd"}, True, [0], dict(batch=0), ("device build",)),
+    "flow-bitmask": ("fm_flow_loss_fused_bitmask", "depth_layout", FLOW5[:1], NO_ADAM, True, [0], dict(batch=0), ("device build",)),
+    "pack": ("fm_flow_pack_inputs_views", "layouts", PACK4, set(), False, [0, 1, 2, 3], dict(batch=0), ("device build",)),
+    "pack-bitmask": ("fm_flow_pack_inputs_bitmask_views", "layouts", PACK4, set(), False, [0, 1, 2, 3], dict(batch=0), ("device build",)),
+    "masks-binary": ("fm_flow_masks_binary", "layouts", [(N, 2), (N, 2)], set(), False, [], dict(batch=0), ("device build",)),
+    "fit": ("fm_procrustes_fit_views", "layouts", PROC4, {"surfaces"}, False, [], dict(points=0), ("device build",)),
+    "fit-chain": ("fm_procrustes_fit_chain_views", "layouts", PROC4, {"surfaces", "corr_out", "tap_records"}, False, [], dict(points=0), ("device build",)),
+    "scatter": ("fm_procrustes_scatter_views", "layouts", PROC4, {"surfaces"}, False, [], dict(points=0), ("device build",)),
+    "scatter-plan": ("fm_procrustes_scatter_plan_views", "flow_layout", [(2 * N, 2)], set(), False, [], dict(points=0), ("device build",)),
+    "residuals": ("fm_flow_residuals", "layouts", FLOW5, set(), True, [], dict(batch=0), ("device build", "host double")),
+}
+
+
+def _view_cases():
+    for label, (_, _, stacks, _, overlap, mod4, invalid, _) in VIEW_ENTRIES.items():
+        for i, (per_frame, frames_of) in enumerate(stacks):
+            yield f"{label}-stack{i}-frames-overlap", label, {i: (per_frame - 1, per_frame * frames_of)}, {}
+            if overlap:
+                yield f"{label}-stack{i}-batch-entries-overlap", label, {i: (per_frame, per_frame * frames_of - 1)}, {}
+            if i in mod4:
+                yield f"{label}-stack{i}-frames-overlap-by-4", label, {i: (per_frame - 4, per_frame * frames_of)}, {}
+                yield f"{label}-stack{i}-frame_stride%4", label, {i: (per_frame + 2, 4 * (per_frame + 2) * frames_of)}, {}
+                yield f"{label}-stack{i}-batch_stride%4", label, {i: (per_frame, per_frame * frames_of + 2)}, {}
+        yield f"{label}-dense-as-zeros", label, {}, invalid
+        yield f"{label}-dense-as-null", label, None, invalid
+
+
+VIEW_REFUSED = list(_view_cases())
+ADAM_ENTRIES = {
+    "fm_flow_loss_fused_adam": {"packed"},
+    "fm_flow_loss_fused_taps": {"packed"},
+    "fm_flow_loss_fused_bitmask": {"depth_layout", "taps"},
+}
+ADAM_REFUSED = [(name, change) for name in ADAM_ENTRIES for change in (dict(beta1=1.0), dict(step=0), dict(exp_avg="misaligned"), dict(touched=None))]
+
+
+def _host_arguments(name, values, null, raw, layouts=None, layout_param=None):
+    """The arguments of entry ``name``: numbers from ``values``, every pointer the 64-byte-aligned address inside ``raw`` (host memory,
+    never dereferenced) unless it is in ``null`` / None in ``values``.  -> (args, what they point at: keep it alive over the call)."""
+    address = (ctypes.addressof(raw) + 63) & ~63
+    taps = (ctypes.c_void_p * 6)(*[address] * 6)  # include/flowmap_hip.h: fm_flow_taps, six pointers (the launcher reads the struct itself)
+    names = [re.search(r"(\w+)\s*$", a).group(1) for a in dict(DECLS)[name].split(",")]
+    args = []
+    for param, kind in zip(names, _lib.SIGNATURES[name], strict=True):
+        if kind is not ctypes.c_void_p:
+            args.append(values[param])
+        elif param == layout_param:
+            args.append(None if layouts is None else ctypes.addressof(layouts))
+        elif param in null or (param in values and values[param] is None):
+            args.append(None)
+        elif param == "taps":
+            args.append(ctypes.addressof(taps))
+        else:
+            args.append(address + 4 if values.get(param) == "misaligned" else address)
+    return args, taps
+
+
+@pytest.mark.parametrize("label,strides,change", [c[1:] for c in VIEW_REFUSED], ids=[c[0] for c in VIEW_REFUSED])
+def test_bad_layouts_are_refused(both_builds, label, strides, change):
+    """frame_stride below a frame, batch entries that overlap, strides the 16-byte routes cannot take, and the two spellings of "dense"
+    ({0, 0} and NULL) beside an invalid argument: status 1, each at the entries whose launcher checks it."""
+    from flowmap_amd._base import FmLayout
+
+    name, layout_param, stacks, null, _, _, _, builds = VIEW_ENTRIES[label]
+    layouts = None
+    if strides is not None:
+        layouts = (FmLayout * len(stacks))()
+        for i, (frame_stride, batch_stride) in strides.items():
+            layouts[i].frame_stride, layouts[i].batch_stride = frame_stride, batch_stride
+    raw = ctypes.create_string_buffer(4096 + 64)
+    args, _alive = _host_arguments(name, {**VIEW_VALID, **change}, null | {"stream"}, raw, layouts, layout_param)
+    for build in builds:
+        assert _entry(both_builds[build], name)(*args) == 1, f"{build}: {name} did not refuse ({label}: {strides}, {change})"
+
+
+@pytest.mark.parametrize("name,change", ADAM_REFUSED, ids=[f"{n}-{k}={v}" for n, c in ADAM_REFUSED for k, v in c.items()])
+def test_bad_adam_arguments_of_the_flow_pass_are_refused(both_builds, name, change):
+    """The in-pass Adam update: beta1 outside [0, 1), step 0, a moment off the 16-byte grid, `touched` missing -> status 1."""
+    raw = ctypes.create_string_buffer(4096 + 64)
+    args, _alive = _host_arguments(name, {**VIEW_VALID, **change}, ADAM_ENTRIES[name] | {"stream"}, raw)
+    assert _entry(both_builds["device build"], name)(*args) == 1, f"{name} did not refuse ({change})"
+
+
 def test_track_tile_constant_matches_header():
     from flowmap_amd import _ops
 
