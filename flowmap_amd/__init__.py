@@ -25,9 +25,9 @@ from .graph import GraphedShardedStep, GraphedStep  # noqa: F401
 from .host import freeze_gc  # noqa: F401
 from ._ops import release_flow_originals  # noqa: F401
 from .optim import FusedAdam  # noqa: F401
-from .types import AlignmentResiduals, BackboneOutput, Batch, DepthConsistency, FlowResiduals, Flows, FocalSweep, ModelOutput, RenderedViews, TrackResiduals, Tracks, TsdfVolume, VoxelCloud  # noqa: F401
+from .types import AlignmentResiduals, BackboneOutput, Batch, DepthConsistency, FlowResiduals, Flows, FocalSweep, ModelOutput, RenderedViews, TrackResiduals, Tracks, TsdfMesh, TsdfVolume, VoxelCloud  # noqa: F401
 
 __all__ = [
     "config", "loss", "model", "install", "uninstall", "set_lazy_surfaces", "depth_consistency", "render_views", "voxel_point_cloud", "tsdf_volume", "FusedAdam", "GraphedStep", "GraphedShardedStep", "freeze_gc", "release_flow_originals",
-    "Batch", "BackboneOutput", "AlignmentResiduals", "DepthConsistency", "FlowResiduals", "FocalSweep", "RenderedViews", "TrackResiduals", "Flows", "ModelOutput", "Tracks", "TsdfVolume", "VoxelCloud", "ExtrinsicsRegressed", "ExtrinsicsRegressedCfg",
+    "Batch", "BackboneOutput", "AlignmentResiduals", "DepthConsistency", "FlowResiduals", "FocalSweep", "RenderedViews", "TrackResiduals", "Flows", "ModelOutput", "Tracks", "TsdfMesh", "TsdfVolume", "VoxelCloud", "ExtrinsicsRegressed", "ExtrinsicsRegressedCfg",
 ]

@@ -133,6 +133,8 @@ SIGNATURES = {
     "fm_tsdf_surface_blocks": [I, I, I, P],
     "fm_tsdf_surface_count": [P, P, I, I, I, I, P, P],
     "fm_tsdf_surface_emit": [P] * 4 + [I, I, I, F, F, F, F, I, P, L] + [P] * 5,
+    "fm_tsdf_mesh_count": [P, P, I, I, I, I, P, P, P],
+    "fm_tsdf_mesh_emit": [P] * 4 + [I, I, I, F, F, F, F, I, P, P, L, L] + [P] * 8,
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -919,6 +919,14 @@ def tsdf_surface(tsdf, weight, color, color_weight, origin, voxel_size, min_weig
     return xyz, normals, (rgb if color is not None else None), edge
 
 
+def tsdf_mesh(tsdf, weight, color, color_weight, origin, voxel_size, min_weight):
+    """The surface-nets mesh of a TSDF volume (csrc/fm_torch.cpp: tsdf_mesh_op -> fm_tsdf_mesh_count, two cumulative sums,
+    fm_tsdf_mesh_emit): (vertices, normals, rgb, cell, faces, edge) — rgb None without ``color``.  Waits for the device once, to size the
+    outputs; one int32 per voxel of workspace."""
+    xyz, normals, rgb, cell, faces, edge = torch_ops().tsdf_mesh(tsdf, weight, color, color_weight, *(float(v) for v in origin), float(voxel_size), int(min_weight))
+    return xyz, normals, (rgb if color is not None else None), cell, faces, edge
+
+
 def softmin_intrinsics(depth, weights, bwd_flow, indices, candidate_k, rel, weight_sens, frames):
     """-> (K (b,frames,3,3) blended over the candidates, softmin weights (b,n)): SoftminScore followed by the tail of
     IntrinsicsSoftmin.forward (intrinsics_softmin.py:105-141), csrc/fm_torch.cpp: SoftminIntrinsics.  K⁻¹ comes out of

@@ -1,5 +1,5 @@
 // Argument checks and size formulas of the residual entry points (include/flowmap_hip.h: fm_flow_residuals, fm_track_residuals,
-// fm_alignment_residuals, fm_focal_sweep, fm_depth_consistency, fm_render_views, fm_voxel_cloud, fm_tsdf_volume, fm_tsdf_surface_count / _emit and their size functions) and the fm_layout rules of the `_views` entry points, stated ONCE: the device build (fm_*.hip) and the serial host build of
+// fm_alignment_residuals, fm_focal_sweep, fm_depth_consistency, fm_render_views, fm_voxel_cloud, fm_tsdf_volume, fm_tsdf_surface_count / _emit, fm_tsdf_mesh_count / _emit and their size functions) and the fm_layout rules of the `_views` entry points, stated ONCE: the device build (fm_*.hip) and the serial host build of
 // the same ABI (fm_*_host.h) both call these, so the two refuse the same calls and size the same workspaces.  Plain C++, no HIP.
 // Device-only, and therefore not here: the 16-byte path's eligibility and the pointer alignment the kernels need (the host build reads
 // element by element and never touches the workspace).
@@ -222,7 +222,7 @@ static inline bool voxel_cloud_args_ok(const float* depth, const float* kinv, co
 }
 
 // ---- TSDF volume ----
-constexpr int kTsdfTile = 256;              // voxels per workgroup of tsdf_integrate_kernel and of the two surface kernels (x fastest)
+constexpr int kTsdfTile = 256;              // voxels per workgroup of tsdf_integrate_kernel, of the two surface kernels and of the three mesh kernels (x fastest)
 constexpr long kTsdfMaxVoxels = 1L << 31;   // nx·ny·nz stays below this: a voxel index is an int32, an edge id (voxel·3 + axis) an int64
 static inline bool tsdf_dims_ok(int nx, int ny, int nz) {
   return nx >= 1 && ny >= 1 && nz >= 1 && (long)nx * ny < kTsdfMaxVoxels && (long)nx * ny * nz < kTsdfMaxVoxels;
@@ -256,6 +256,22 @@ static inline bool tsdf_surface_emit_args_ok(const float* tsdf, const int32_t* w
   if (!(tsdf && weight && block_offsets && xyz && normals && edge)) return false;
   if ((color != nullptr) != (color_weight != nullptr) || (color != nullptr) != (rgb != nullptr)) return false;
   return tsdf_dims_ok(nx, ny, nz) && tsdf_grid_ok(ox, oy, oz, voxel_size) && min_weight >= 1 && rows >= 1;
+}
+
+static inline bool tsdf_mesh_count_args_ok(const float* tsdf, const int32_t* weight, int nx, int ny, int nz, int min_weight, const int64_t* cell_counts,
+                                           const int64_t* quad_counts) {
+  return tsdf && weight && cell_counts && quad_counts && tsdf_dims_ok(nx, ny, nz) && min_weight >= 1;
+}
+
+// (a mesh has vertices; it may have no quad — one active cell at the rim — and then takes no quad_offsets, faces or edge)
+static inline bool tsdf_mesh_emit_args_ok(const float* tsdf, const int32_t* weight, const float* color, const int32_t* color_weight, int nx, int ny, int nz,
+                                          float ox, float oy, float oz, float voxel_size, int min_weight, const int64_t* cell_offsets,
+                                          const int64_t* quad_offsets, long vertex_rows, long quad_rows, const float* xyz, const float* normals,
+                                          const float* rgb, const int64_t* cell, const int32_t* cell_vertex, const int32_t* faces, const int64_t* edge) {
+  if (!(tsdf && weight && cell_offsets && xyz && normals && cell && cell_vertex)) return false;
+  if ((color != nullptr) != (color_weight != nullptr) || (color != nullptr) != (rgb != nullptr)) return false;
+  if (vertex_rows < 1 || quad_rows < 0 || (quad_rows > 0 && !(quad_offsets && faces && edge))) return false;
+  return tsdf_dims_ok(nx, ny, nz) && tsdf_grid_ok(ox, oy, oz, voxel_size) && min_weight >= 1;
 }
 
 }  // namespace fm

@@ -52,7 +52,8 @@ using OptTensor = std::optional<Tensor>;
   X(fm_random_subset) X(fm_random_subset_stateful) X(fm_abi_version) X(fm_flow_loss_fused_taps) X(fm_track_loss_fused_fwd_taps) X(fm_tap_grad_apply) \
   X(fm_flow_loss_fused_bitmask) X(fm_flow_residuals) X(fm_flow_residual_blocks) X(fm_track_residuals) X(fm_track_residual_workspace) \
   X(fm_depth_consistency) X(fm_depth_consistency_blocks) X(fm_render_views) X(fm_render_views_workspace) \
-  X(fm_voxel_cloud) X(fm_voxel_cloud_workspace) X(fm_tsdf_volume) X(fm_tsdf_surface_blocks) X(fm_tsdf_surface_count) X(fm_tsdf_surface_emit)
+  X(fm_voxel_cloud) X(fm_voxel_cloud_workspace) X(fm_tsdf_volume) X(fm_tsdf_surface_blocks) X(fm_tsdf_surface_count) X(fm_tsdf_surface_emit) \
+  X(fm_tsdf_mesh_count) X(fm_tsdf_mesh_emit)
 
 struct Api {
 #define X(name) decltype(&::name) name = nullptr;
@@ -1796,29 +1797,41 @@ static std::vector<Tensor> tsdf_volume_op(const Tensor& depth_in, const Tensor& 
   return {w2c, tsdf, weight, color, color_weight};
 }
 
+// The fields of a finished volume as tsdf_surface_op and tsdf_mesh_op take them: on one device, contiguous, tsdf (nz,ny,nx) float32, weight
+// int32 of the same shape, color (nz,ny,nx,3) float32 and color_weight int32 together or not at all.  `op` goes into the messages.
+struct TsdfFields {
+  c10::Device dev;
+  bool has_color = false;
+  Tensor tsdf, weight, color, cw;
+  int64_t nx = 0, ny = 0, nz = 0;
+};
+static TsdfFields tsdf_fields(const char* op, const Tensor& tsdf_in, const Tensor& weight_in, const OptTensor& color_in, const OptTensor& color_weight_in) {
+  const bool has_color = color_in.has_value() && color_in->defined();
+  TORCH_CHECK(has_color == (color_weight_in.has_value() && color_weight_in->defined()), "flowmap_amd: ", op, ": color and color_weight go together");
+  const Tensor color_t = has_color ? *color_in : Tensor(), cw_t = has_color ? *color_weight_in : Tensor();
+  TsdfFields v{check_device({&tsdf_in, &weight_in, &color_t, &cw_t}), has_color};
+  v.tsdf = f32c(tsdf_in.detach(), "tsdf");
+  TORCH_CHECK(v.tsdf.dim() == 3 && weight_in.scalar_type() == at::kInt && weight_in.sizes() == v.tsdf.sizes(), "flowmap_amd: ", op,
+              ": tsdf must be (nz, ny, nx) float32 and weight int32 of the same shape");
+  v.weight = weight_in.contiguous();
+  const int64_t nz = v.nz = v.tsdf.size(0), ny = v.ny = v.tsdf.size(1), nx = v.nx = v.tsdf.size(2);
+  TORCH_CHECK(nx >= 1 && ny >= 1 && nz >= 1 && nx * ny * nz < (int64_t(1) << 31), "flowmap_amd: ", op, ": the grid must hold 1 to 2^31 - 1 voxels");
+  if (has_color) {
+    v.color = f32c(color_t.detach(), "color");
+    TORCH_CHECK(v.color.sizes() == at::IntArrayRef({nz, ny, nx, 3}) && cw_t.scalar_type() == at::kInt && cw_t.sizes() == v.tsdf.sizes(), "flowmap_amd: ", op,
+                ": color must be (nz, ny, nx, 3) float32 and color_weight int32 shaped like tsdf");
+    v.cw = cw_t.contiguous();
+  }
+  return v;
+}
+
 // TsdfVolume.surface_points (fm_tsdf_surface_count, fm_tsdf_surface_emit): the zero crossings of a volume in ascending edge id.  -> {xyz,
 // normals, rgb (empty without color), edge int64}.  The count pass, an exclusive cumulative sum of the per-workgroup counts and the read of
 // their total (the one synchronisation: it sizes the output), then the emit pass.
 static std::vector<Tensor> tsdf_surface_op(const Tensor& tsdf_in, const Tensor& weight_in, const OptTensor& color_in, const OptTensor& color_weight_in, double ox,
                                            double oy, double oz, double voxel_size, int64_t min_weight) {
   at::NoGradGuard no_grad;
-  const bool has_color = color_in.has_value() && color_in->defined();
-  TORCH_CHECK(has_color == (color_weight_in.has_value() && color_weight_in->defined()), "flowmap_amd: surface_points: color and color_weight go together");
-  const Tensor color_t = has_color ? *color_in : Tensor(), cw_t = has_color ? *color_weight_in : Tensor();
-  const auto dev = check_device({&tsdf_in, &weight_in, &color_t, &cw_t});
-  const Tensor tsdf = f32c(tsdf_in.detach(), "tsdf");
-  TORCH_CHECK(tsdf.dim() == 3 && weight_in.scalar_type() == at::kInt && weight_in.sizes() == tsdf.sizes(),
-              "flowmap_amd: surface_points: tsdf must be (nz, ny, nx) float32 and weight int32 of the same shape");
-  const Tensor weight = weight_in.contiguous();
-  const int64_t nz = tsdf.size(0), ny = tsdf.size(1), nx = tsdf.size(2);
-  TORCH_CHECK(nx >= 1 && ny >= 1 && nz >= 1 && nx * ny * nz < (int64_t(1) << 31), "flowmap_amd: surface_points: the grid must hold 1 to 2^31 - 1 voxels");
-  Tensor color, cw;
-  if (has_color) {
-    color = f32c(color_t.detach(), "color");
-    TORCH_CHECK(color.sizes() == at::IntArrayRef({nz, ny, nx, 3}) && cw_t.scalar_type() == at::kInt && cw_t.sizes() == tsdf.sizes(),
-                "flowmap_amd: surface_points: color must be (nz, ny, nx, 3) float32 and color_weight int32 shaped like tsdf");
-    cw = cw_t.contiguous();
-  }
+  const auto [dev, has_color, tsdf, weight, color, cw, nx, ny, nz] = tsdf_fields("surface_points", tsdf_in, weight_in, color_in, color_weight_in);
   long blocks = 0;
   FM_CALL(fm_tsdf_surface_blocks, (int)nx, (int)ny, (int)nz, &blocks);
   const auto fopt = tsdf.options();
@@ -1836,6 +1849,37 @@ static std::vector<Tensor> tsdf_surface_op(const Tensor& tsdf_in, const Tensor& 
             has_color ? ptr(rgb) : nullptr, ptr<int64_t>(edge), scope.stream);
   }
   return {xyz, normals, rgb, edge};
+}
+
+// TsdfVolume.mesh (fm_tsdf_mesh_count, fm_tsdf_mesh_emit): the surface-nets mesh of a volume.  -> {vertices, normals, rgb (empty without
+// color), cell int64, faces (2Q,3) int32, edge (Q) int64}.  The count pass, the exclusive cumulative sums of both rows of per-workgroup
+// counts, ONE copy of the two totals to the host (the one synchronisation: it sizes the outputs), then the vertex and the face pass.
+// cell_vertex, one int32 per voxel, is the only workspace; the vertex pass fills all of it.
+static std::vector<Tensor> tsdf_mesh_op(const Tensor& tsdf_in, const Tensor& weight_in, const OptTensor& color_in, const OptTensor& color_weight_in, double ox,
+                                        double oy, double oz, double voxel_size, int64_t min_weight) {
+  at::NoGradGuard no_grad;
+  const auto [dev, has_color, tsdf, weight, color, cw, nx, ny, nz] = tsdf_fields("mesh", tsdf_in, weight_in, color_in, color_weight_in);
+  long blocks = 0;
+  FM_CALL(fm_tsdf_surface_blocks, (int)nx, (int)ny, (int)nz, &blocks);
+  const auto fopt = tsdf.options(), lopt = fopt.dtype(at::kLong), iopt = fopt.dtype(at::kInt);
+  Tensor counts = at::empty({2, (int64_t)blocks}, lopt);  // row 0: active cells, row 1: quads
+  DeviceScope scope(dev);
+  FM_CALL(fm_tsdf_mesh_count, ptr(tsdf), ptr<int32_t>(weight), (int)nx, (int)ny, (int)nz, (int)min_weight, ptr<int64_t>(counts), ptr<int64_t>(counts) + blocks,
+          scope.stream);
+  const Tensor ends = at::cumsum(counts, 1);
+  const Tensor totals = ends.select(1, blocks - 1).cpu();
+  const int64_t vertices = totals[0].item<int64_t>(), quads = totals[1].item<int64_t>();
+  Tensor xyz = at::empty({vertices, 3}, fopt), normals = at::empty({vertices, 3}, fopt), rgb = has_color ? at::empty({vertices, 3}, fopt) : at::empty({0}, fopt);
+  Tensor cell = at::empty({vertices}, lopt), faces = at::empty({2 * quads, 3}, iopt), edge = at::empty({quads}, lopt);
+  if (vertices > 0) {
+    const Tensor offsets = (ends - counts).contiguous();
+    Tensor cell_vertex = at::empty({nz * ny * nx}, iopt);
+    FM_CALL(fm_tsdf_mesh_emit, ptr(tsdf), ptr<int32_t>(weight), has_color ? ptr(color) : nullptr, has_color ? ptr<int32_t>(cw) : nullptr, (int)nx, (int)ny, (int)nz,
+            (float)ox, (float)oy, (float)oz, (float)voxel_size, (int)min_weight, ptr<int64_t>(offsets), ptr<int64_t>(offsets) + blocks, (long)vertices, (long)quads,
+            ptr(xyz), ptr(normals), has_color ? ptr(rgb) : nullptr, ptr<int64_t>(cell), ptr<int32_t>(cell_vertex), quads > 0 ? ptr<int32_t>(faces) : nullptr,
+            quads > 0 ? ptr<int64_t>(edge) : nullptr, scope.stream);
+  }
+  return {xyz, normals, rgb, cell, faces, edge};
 }
 
 }  // namespace fmt
@@ -1932,4 +1976,6 @@ TORCH_LIBRARY(flowmap_amd, m) {
         fmt::tsdf_volume_op);
   m.def("tsdf_surface(Tensor tsdf, Tensor weight, Tensor? color, Tensor? color_weight, float ox, float oy, float oz, float voxel_size, int min_weight) -> Tensor[]",
         fmt::tsdf_surface_op);
+  m.def("tsdf_mesh(Tensor tsdf, Tensor weight, Tensor? color, Tensor? color_weight, float ox, float oy, float oz, float voxel_size, int min_weight) -> Tensor[]",
+        fmt::tsdf_mesh_op);
 }

@@ -18,11 +18,17 @@
 // edge ids (edge = voxel·3 + axis).  The count pass writes the crossings of each workgroup; the caller turns the counts into exclusive
 // offsets (the one synchronisation that sizes the output); the emit pass repeats the decisions, ranks its threads with a scan through
 // LDS and writes each row at offset + rank — rows in ascending edge id with no atomics and no sort.
+//
+// tsdf_mesh_count_kernel / tsdf_mesh_vertex_kernel / tsdf_mesh_face_kernel (TsdfVolume.mesh; fm_tsdf_mesh_count, fm_tsdf_mesh_emit): the
+// surface-nets mesh of the volume by the same count, cumulative sum, emit scheme.  The vertex pass writes one vertex per active cell in
+// ascending cell id and, for EVERY voxel, its row or −1 into `cell_vertex`; the face pass, after it on the same stream, looks the four
+// cells of each quad up there and writes two triangles per quad in ascending edge id.
 #include <hip/hip_runtime.h>
 
 #include "../../include/flowmap_hip.h"
 #include "fm_device.h"
 #include "fm_residual_args.h"
+#include "fm_tsdf_mesh.h"
 
 namespace fm {
 
@@ -157,6 +163,79 @@ __global__ void __launch_bounds__(kTsdfThreads) tsdf_surface_emit_kernel(TsdfGri
   }
 }
 
+// ---- the mesh (fm_tsdf_mesh.h: surface nets) — the same tiling: the thread owns the cell whose low corner is its voxel, and that voxel's
+// three edges.  A workgroup holds at most 256 active cells and 768 quads, so the two counts share one scan, 16 bits each.
+
+// The crossings of this thread's cell (12 bits; 0 past the grid or where the cell does not exist).
+__device__ __forceinline__ int tsdf_thread_cell(const TsdfGrid& g, long voxels, long voxel, int ijk[3]) {
+  if (voxel >= voxels) return 0;
+  tsdf_voxel_ijk(g, voxel, ijk);
+  return tsdf_cell_crossings(g, voxel, ijk);
+}
+
+__global__ void __launch_bounds__(kTsdfThreads) tsdf_mesh_count_kernel(TsdfGrid g, long voxels, int64_t* cell_counts, int64_t* quad_counts) {
+  __shared__ int lds[kTsdfThreads];
+  int ijk[3] = {0, 0, 0};
+  const long voxel = (long)blockIdx.x * kTsdfThreads + threadIdx.x;
+  const int bits = tsdf_thread_cell(g, voxels, voxel, ijk);
+  const int quads = bits ? tsdf_voxel_quads(g, ijk, bits) : 0;
+  const int total = tsdf_block_scan((bits ? 1 : 0) | (__popc(quads) << 16), lds);
+  if (threadIdx.x == kTsdfThreads - 1) {
+    cell_counts[blockIdx.x] = total & 0xffff;
+    quad_counts[blockIdx.x] = total >> 16;
+  }
+}
+
+template <bool COLOR>
+__global__ void __launch_bounds__(kTsdfThreads) tsdf_mesh_vertex_kernel(TsdfGrid g, long voxels, const int64_t* cell_offsets, long rows, float* xyz, float* normals,
+                                                                        float* rgb, int64_t* cell, int32_t* cell_vertex) {
+  __shared__ int lds[kTsdfThreads];
+  int ijk[3] = {0, 0, 0};
+  const long voxel = (long)blockIdx.x * kTsdfThreads + threadIdx.x;
+  const int bits = tsdf_thread_cell(g, voxels, voxel, ijk);
+  const int mine = bits ? 1 : 0;
+  const long row = cell_offsets[blockIdx.x] + (long)(tsdf_block_scan(mine, lds) - mine);
+  const bool write = mine && row >= 0 && row < rows;  // (the caller sized the outputs from the count pass on the same volume: always true then)
+  if (voxel < voxels) cell_vertex[voxel] = write ? (int32_t)row : -1;  // EVERY voxel: the face pass reads it without a memset before
+  if (!write) return;
+  float point[3], normal[3], colour[3];
+  tsdf_cell_vertex(g, voxel, ijk, bits, COLOR, point, normal, colour);  // (a compile-time flag: a run-time one kept `colour` on the stack)
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    xyz[row * 3 + e] = point[e];
+    normals[row * 3 + e] = normal[e];
+    if (COLOR) rgb[row * 3 + e] = colour[e];
+  }
+  cell[row] = (int64_t)voxel;
+}
+
+__global__ void __launch_bounds__(kTsdfThreads) tsdf_mesh_face_kernel(TsdfGrid g, long voxels, const int64_t* quad_offsets, long rows,
+                                                                      const int32_t* cell_vertex, int32_t* faces, int64_t* edge) {
+  __shared__ int lds[kTsdfThreads];
+  int ijk[3] = {0, 0, 0};
+  const long voxel = (long)blockIdx.x * kTsdfThreads + threadIdx.x;
+  const int bits = tsdf_thread_cell(g, voxels, voxel, ijk);
+  const int quads = bits ? tsdf_voxel_quads(g, ijk, bits) : 0;
+  const int mine = __popc(quads);
+  long row = quad_offsets[blockIdx.x] + (long)(tsdf_block_scan(mine, lds) - mine);
+  if (!quads) return;
+  const bool low_negative = g.tsdf[voxel] < 0.f;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (!(quads & (1 << a))) continue;
+    if (row >= 0 && row < rows) {
+      long cells[4];
+      tsdf_quad_cells(g, voxel, a, low_negative, cells);  // (inside the grid: tsdf_edge_has_quad)
+      const int32_t q0 = cell_vertex[cells[0]], q1 = cell_vertex[cells[1]], q2 = cell_vertex[cells[2]], q3 = cell_vertex[cells[3]];
+      int32_t* to = faces + row * 6;
+      to[0] = q0, to[1] = q1, to[2] = q2;
+      to[3] = q0, to[4] = q2, to[5] = q3;
+      edge[row] = (int64_t)voxel * 3 + a;
+    }
+    ++row;
+  }
+}
+
 static TsdfGrid tsdf_grid(const float* tsdf, const int32_t* weight, const float* color, const int32_t* color_weight, int nx, int ny, int nz, int min_weight,
                           float ox, float oy, float oz, float voxel_size) {
   TsdfGrid g{tsdf, weight, color, color_weight, nx, ny, nz, min_weight, {ox, oy, oz}, voxel_size};
@@ -208,6 +287,33 @@ int fm_tsdf_surface_emit(const float* tsdf, const int32_t* weight, const float* 
   const TsdfGrid g = tsdf_grid(tsdf, weight, color, color_weight, nx, ny, nz, min_weight, ox, oy, oz, voxel_size);
   hipLaunchKernelGGL(tsdf_surface_emit_kernel, dim3((unsigned)tsdf_blocks(voxels)), dim3(kTsdfThreads), 0, (hipStream_t)stream, g, voxels, block_offsets, rows,
                      xyz, normals, rgb, edge);
+  FM_LAUNCH_STATUS();
+}
+
+int fm_tsdf_mesh_count(const float* tsdf, const int32_t* weight, int nx, int ny, int nz, int min_weight, int64_t* cell_counts, int64_t* quad_counts,
+                       void* stream) {
+  FM_CHECK_ARG(tsdf_mesh_count_args_ok(tsdf, weight, nx, ny, nz, min_weight, cell_counts, quad_counts));
+  const long voxels = (long)nx * ny * nz;
+  const TsdfGrid g = tsdf_grid(tsdf, weight, nullptr, nullptr, nx, ny, nz, min_weight, 0.f, 0.f, 0.f, 1.f);
+  hipLaunchKernelGGL(tsdf_mesh_count_kernel, dim3((unsigned)tsdf_blocks(voxels)), dim3(kTsdfThreads), 0, (hipStream_t)stream, g, voxels, cell_counts,
+                     quad_counts);
+  FM_LAUNCH_STATUS();
+}
+
+int fm_tsdf_mesh_emit(const float* tsdf, const int32_t* weight, const float* color, const int32_t* color_weight, int nx, int ny, int nz, float ox, float oy,
+                      float oz, float voxel_size, int min_weight, const int64_t* cell_offsets, const int64_t* quad_offsets, long vertex_rows, long quad_rows,
+                      float* xyz, float* normals, float* rgb, int64_t* cell, int32_t* cell_vertex, int32_t* faces, int64_t* edge, void* stream) {
+  FM_CHECK_ARG(tsdf_mesh_emit_args_ok(tsdf, weight, color, color_weight, nx, ny, nz, ox, oy, oz, voxel_size, min_weight, cell_offsets, quad_offsets,
+                                      vertex_rows, quad_rows, xyz, normals, rgb, cell, cell_vertex, faces, edge));
+  const long voxels = (long)nx * ny * nz;
+  const TsdfGrid g = tsdf_grid(tsdf, weight, color, color_weight, nx, ny, nz, min_weight, ox, oy, oz, voxel_size);
+  const dim3 grid((unsigned)tsdf_blocks(voxels));
+  if (rgb) hipLaunchKernelGGL(tsdf_mesh_vertex_kernel<true>, grid, dim3(kTsdfThreads), 0, (hipStream_t)stream, g, voxels, cell_offsets, vertex_rows, xyz, normals,
+                              rgb, cell, cell_vertex);
+  else hipLaunchKernelGGL(tsdf_mesh_vertex_kernel<false>, grid, dim3(kTsdfThreads), 0, (hipStream_t)stream, g, voxels, cell_offsets, vertex_rows, xyz, normals,
+                          rgb, cell, cell_vertex);
+  if (quad_rows > 0)  // (the same stream: the face pass reads the cell_vertex the vertex pass has just filled)
+    hipLaunchKernelGGL(tsdf_mesh_face_kernel, grid, dim3(kTsdfThreads), 0, (hipStream_t)stream, g, voxels, quad_offsets, quad_rows, cell_vertex, faces, edge);
   FM_LAUNCH_STATUS();
 }
 

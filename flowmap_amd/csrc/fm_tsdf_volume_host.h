@@ -1,17 +1,19 @@
-// TSDF fusion (include/flowmap_hip.h, ABI version 16) for a HOST build of the C ABI.
+// TSDF fusion (include/flowmap_hip.h, ABI versions 16 and 17) for a HOST build of the C ABI.
 //
 // fm_math.h includes this file when it is compiled by a plain host compiler — the serial build of the ABI that the CPU test-suite links
 // the package against instead of libflowmap_hip.so — and never under hipcc.  Per voxel and frame it calls tsdf_centre, tsdf_pixel_of,
 // tsdf_term and tsdf_finish, per edge tsdf_edge_crosses and tsdf_edge_point (fm_math.h): the very functions the device kernels
 // (fm_tsdf_volume.hip) call, in the same order — voxels ascending, frames ascending inside a voxel, edges ascending.  The count pass
 // writes the same per-workgroup counts (kTsdfTile voxels each) and the emit pass starts each workgroup at its offset, so the two builds
-// take the same `block_counts` / `block_offsets`.
+// take the same `block_counts` / `block_offsets`.  The mesh entries (ABI version 17: fm_tsdf_mesh_count, fm_tsdf_mesh_emit) do the same
+// with the per-cell and per-quad functions of fm_tsdf_mesh.h: the vertex pass over all workgroups, then the face pass.
 #pragma once
 
 #include <cstddef>
 
 #include "../../include/flowmap_hip.h"
 #include "fm_residual_args.h"
+#include "fm_tsdf_mesh.h"
 
 extern "C" {
 
@@ -102,6 +104,78 @@ int fm_tsdf_surface_emit(const float* tsdf, const int32_t* weight, const float* 
           fm::tsdf_edge_point(g, voxel, ijk, a, rgb != nullptr, xyz + row * 3, normals + row * 3, colour);
           if (rgb)
             for (int e = 0; e < 3; ++e) rgb[row * 3 + e] = colour[e];
+          edge[row] = (int64_t)voxel * 3 + a;
+        }
+        ++row;
+      }
+    }
+  }
+  return 0;
+}
+
+int fm_tsdf_mesh_count(const float* tsdf, const int32_t* weight, int nx, int ny, int nz, int min_weight, int64_t* cell_counts, int64_t* quad_counts, void*) {
+  if (!fm::tsdf_mesh_count_args_ok(tsdf, weight, nx, ny, nz, min_weight, cell_counts, quad_counts)) return 1;
+  const fm::TsdfGrid g{tsdf, weight, nullptr, nullptr, nx, ny, nz, min_weight, {0.f, 0.f, 0.f}, 1.f};
+  const long voxels = (long)nx * ny * nz, blocks = fm::tsdf_blocks(voxels);
+  for (long b = 0; b < blocks; ++b) {
+    int64_t cells = 0, quads = 0;
+    for (long voxel = b * fm::kTsdfTile; voxel < voxels && voxel < (b + 1) * fm::kTsdfTile; ++voxel) {
+      int ijk[3];
+      fm::tsdf_voxel_ijk(g, voxel, ijk);
+      const int bits = fm::tsdf_cell_crossings(g, voxel, ijk);
+      if (!bits) continue;
+      cells += 1;
+      quads += __builtin_popcount(fm::tsdf_voxel_quads(g, ijk, bits));
+    }
+    cell_counts[b] = cells;
+    quad_counts[b] = quads;
+  }
+  return 0;
+}
+
+int fm_tsdf_mesh_emit(const float* tsdf, const int32_t* weight, const float* color, const int32_t* color_weight, int nx, int ny, int nz, float ox, float oy,
+                      float oz, float voxel_size, int min_weight, const int64_t* cell_offsets, const int64_t* quad_offsets, long vertex_rows, long quad_rows,
+                      float* xyz, float* normals, float* rgb, int64_t* cell, int32_t* cell_vertex, int32_t* faces, int64_t* edge, void*) {
+  if (!fm::tsdf_mesh_emit_args_ok(tsdf, weight, color, color_weight, nx, ny, nz, ox, oy, oz, voxel_size, min_weight, cell_offsets, quad_offsets, vertex_rows,
+                                  quad_rows, xyz, normals, rgb, cell, cell_vertex, faces, edge))
+    return 1;
+  const fm::TsdfGrid g{tsdf, weight, color, color_weight, nx, ny, nz, min_weight, {ox, oy, oz}, voxel_size};
+  const long voxels = (long)nx * ny * nz, blocks = fm::tsdf_blocks(voxels);
+  for (long b = 0; b < blocks; ++b) {  // the vertex pass: every voxel's cell_vertex is written
+    long row = (long)cell_offsets[b];
+    for (long voxel = b * fm::kTsdfTile; voxel < voxels && voxel < (b + 1) * fm::kTsdfTile; ++voxel) {
+      int ijk[3];
+      fm::tsdf_voxel_ijk(g, voxel, ijk);
+      const int bits = fm::tsdf_cell_crossings(g, voxel, ijk);
+      const bool write = bits != 0 && row >= 0 && row < vertex_rows;
+      cell_vertex[voxel] = write ? (int32_t)row : -1;
+      if (write) {
+        float colour[3];
+        fm::tsdf_cell_vertex(g, voxel, ijk, bits, rgb != nullptr, xyz + row * 3, normals + row * 3, colour);
+        if (rgb)
+          for (int e = 0; e < 3; ++e) rgb[row * 3 + e] = colour[e];
+        cell[row] = (int64_t)voxel;
+      }
+      row += bits != 0;
+    }
+  }
+  if (quad_rows == 0) return 0;
+  for (long b = 0; b < blocks; ++b) {  // the face pass
+    long row = (long)quad_offsets[b];
+    for (long voxel = b * fm::kTsdfTile; voxel < voxels && voxel < (b + 1) * fm::kTsdfTile; ++voxel) {
+      int ijk[3];
+      fm::tsdf_voxel_ijk(g, voxel, ijk);
+      const int bits = fm::tsdf_cell_crossings(g, voxel, ijk);
+      const int quads = bits ? fm::tsdf_voxel_quads(g, ijk, bits) : 0;
+      for (int a = 0; a < 3; ++a) {
+        if (!(quads & (1 << a))) continue;
+        if (row >= 0 && row < quad_rows) {
+          long cells[4];
+          fm::tsdf_quad_cells(g, voxel, a, tsdf[voxel] < 0.f, cells);
+          const int32_t q[4] = {cell_vertex[cells[0]], cell_vertex[cells[1]], cell_vertex[cells[2]], cell_vertex[cells[3]]};
+          int32_t* to = faces + row * 6;
+          to[0] = q[0], to[1] = q[1], to[2] = q[2];
+          to[3] = q[0], to[4] = q[2], to[5] = q[3];
           edge[row] = (int64_t)voxel * 3 + a;
         }
         ++row;

@@ -6,9 +6,10 @@
 * ``voxel_point_cloud``: the same points merged per cell of a world-space grid — one averaged point and colour per occupied voxel, a
   count and the lowest contributing pixel —, in ONE pass over depth (fm_voxel_cloud) with no point cloud formed; bit-reproducible.
 * ``tsdf_volume``: the depth maps fused into a truncated-signed-distance grid (fm_tsdf_volume: one thread per voxel walks the frames, no
-  atomics) -> ``TsdfVolume``, whose ``surface_points`` are the zero crossings with normals; ``grid_around`` sizes the grid from a cloud.
+  atomics) -> ``TsdfVolume``, whose ``surface_points`` are the zero crossings with normals and whose ``mesh`` is the surface-nets
+  triangle mesh (``TsdfMesh``); ``grid_around`` sizes the grid from a cloud.
 * ``write_ply``: the vertex layout of colmap.py:31-53 (x y z nx ny nz red green blue, binary
-  little-endian — what 3D Gaussian Splatting reads), written with numpy alone.
+  little-endian — what 3D Gaussian Splatting reads), written with numpy alone; with ``faces`` a triangle face element follows.
 * ``compute_ate``: flowmap/misc/ate.py:7-25 (scipy Procrustes alignment, RMS over all
   coordinates) — tiny, stays on the host.
 The COLMAP camera/image records (colmap.py:114-, third_party/colmap) are file IO and stay with
@@ -217,9 +218,13 @@ _PLY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), 
                        ("red", "u1"), ("green", "u1"), ("blue", "u1")])
 
 
-def write_ply(path: Path, xyz: np.ndarray, rgb: np.ndarray, normals: Optional[np.ndarray] = None) -> None:
+_PLY_FACE_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", 3)])  # `property list uchar int vertex_indices`: a count of 3 and three indices
+
+
+def write_ply(path: Path, xyz: np.ndarray, rgb: np.ndarray, normals: Optional[np.ndarray] = None, faces: Optional[np.ndarray] = None) -> None:
     """colmap.py:31-53: zero normals, colours scaled by 255 and truncated to uint8.  ``normals`` (N, 3): written as nx ny nz instead of the
-    zeros (TsdfVolume.write_ply); without them the file is what it always was."""
+    zeros (TsdfVolume.write_ply); ``faces`` (M, 3) integer rows of ``xyz``: a face element of triangles after the vertices
+    (TsdfMesh.write_ply); without either the file is what it always was."""
     xyz = np.asarray(xyz, dtype=np.float32)
     vertices = np.zeros(xyz.shape[0], dtype=_PLY_DTYPE)
     vertices["x"], vertices["y"], vertices["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
@@ -233,10 +238,22 @@ def write_ply(path: Path, xyz: np.ndarray, rgb: np.ndarray, normals: Optional[np
     kinds = {"<f4": "float", "|u1": "uchar"}
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {xyz.shape[0]}"]
     header += [f"property {kinds[_PLY_DTYPE[name].str]} {name}" for name in _PLY_DTYPE.names]
+    records = None
+    if faces is not None:
+        faces = np.asarray(faces)
+        if faces.ndim != 2 or faces.shape[1] != 3 or not np.issubdtype(faces.dtype, np.integer):
+            raise ValueError(f"flowmap_amd: write_ply: faces must be (M, 3) integers (got {faces.dtype} of shape {faces.shape})")
+        if faces.size and not (0 <= int(faces.min()) and int(faces.max()) < xyz.shape[0]):
+            raise ValueError(f"flowmap_amd: write_ply: faces index rows {int(faces.min())} to {int(faces.max())} of {xyz.shape[0]} points")
+        records = np.zeros(faces.shape[0], dtype=_PLY_FACE_DTYPE)
+        records["n"], records["v"] = 3, faces
+        header += [f"element face {faces.shape[0]}", "property list uchar int vertex_indices"]
     header.append("end_header")
     with open(path, "wb") as handle:
         handle.write(("\n".join(header) + "\n").encode("ascii"))
         handle.write(vertices.tobytes())
+        if records is not None:
+            handle.write(records.tobytes())
 
 
 def read_ply(path: Path) -> Tuple[np.ndarray, np.ndarray]:

@@ -49,9 +49,10 @@ extern "C" {
  * fm_depth_consistency / fm_depth_consistency_blocks; the existing entries are unchanged; version 14: the rendered views —
  * fm_render_views / fm_render_views_workspace; the existing entries are unchanged; version 15: the voxel-fused point cloud —
  * fm_voxel_cloud / fm_voxel_cloud_workspace; the existing entries are unchanged; version 16: the TSDF volume and its surface points —
- * fm_tsdf_volume, fm_tsdf_surface_blocks / fm_tsdf_surface_count / fm_tsdf_surface_emit; the existing entries are unchanged).  A binding checks
+ * fm_tsdf_volume, fm_tsdf_surface_blocks / fm_tsdf_surface_count / fm_tsdf_surface_emit; the existing entries are unchanged; version 17: the
+ * triangle mesh of a TSDF volume — fm_tsdf_mesh_count / fm_tsdf_mesh_emit; the existing entries are unchanged).  A binding checks
  * fm_abi_version() == FM_ABI_VERSION when it loads the library. */
-#define FM_ABI_VERSION 16
+#define FM_ABI_VERSION 17
 int fm_abi_version(void);
 
 #define FM_STAT_STRIDE 16      /* doubles per pair in `stats` */
@@ -1003,6 +1004,33 @@ int fm_tsdf_surface_count(const float* tsdf, const int32_t* weight, int nx, int 
 int fm_tsdf_surface_emit(const float* tsdf, const int32_t* weight, const float* color, const int32_t* color_weight, int nx, int ny, int nz, float ox,
                          float oy, float oz, float voxel_size, int min_weight, const int64_t* block_offsets, long rows, float* xyz, float* normals,
                          float* rgb, int64_t* edge, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * The triangle mesh of a TSDF volume (ABI version 17), by surface nets: no case table.  Cell c has voxel c as its low corner and the seven
+ * voxels at +1 along the axes as its other corners; it exists when i+1 < nx, j+1 < ny, k+1 < nz and is active when one of its 12 edges is
+ * a crossing (above).  The 12 edges in order: axis a = 0, 1, 2; with b = (a+1)%3, c = (a+2)%3 the edge along a from the low corner moved
+ * by (db, dc) = (0,0), (1,0), (0,1), (1,1) along (b, c).
+ *   vertex: one per active cell, in ascending cell id: xyz = the fp32 sum, in that order, of the crossing edges' points divided by their
+ *     number n (contraction off); normal = the sum of their normals divided by its length, 0 where it has none; rgb = the sum of their
+ *     rgb / n; cell = the cell id (fm_tsdf_mesh.h: tsdf_cell_crossings, tsdf_cell_vertex, over tsdf_edge_point as it is).
+ *   quad: a crossing edge voxel·3 + a has one when its four cells exist: 1 <= index_b <= size_b - 2 and 1 <= index_c <= size_c - 2.  Its
+ *     corners are the cells at (db, dc) = (-1,-1), (0,-1), (0,0), (-1,0) from the edge's voxel when the tsdf at the edge's low end is
+ *     negative, in the reverse order otherwise; its triangles (q0, q1, q2) and (q0, q2, q3) then face up the field: out of the surface,
+ *     toward the cameras.  Quads come out in ascending edge id; a crossing on the rim of the grid has a surface point and no quad.
+ * A workgroup owns 256 consecutive voxels — their cells and their edges (fm_tsdf_surface_blocks gives the number of workgroups):
+ *   fm_tsdf_mesh_count: cell_counts, quad_counts (blocks) int64 out = the active cells and the quads of each workgroup's voxels;
+ *   fm_tsdf_mesh_emit: cell_offsets, quad_offsets (blocks) int64 in = their exclusive cumulative sums; vertex_rows >= 1 and
+ *     quad_rows >= 0 = their totals.  xyz, normals (vertex_rows,3), rgb (vertex_rows,3; given exactly when color and color_weight are),
+ *     cell (vertex_rows) int64; cell_vertex (nx·ny·nz) int32 workspace: the vertex pass writes EVERY element — the voxel's row, or -1 — so
+ *     it needs no clearing; faces (2·quad_rows,3) int32, rows 2q and 2q+1 the triangles of quad q, and edge (quad_rows) int64; with
+ *     quad_rows == 0, quad_offsets, faces and edge may be NULL and the face pass is not launched.  A row at or past its total is not
+ *     written.  Two launches on `stream`, the face pass after the vertex pass.  No atomics, no sort: every output element is written once. */
+int fm_tsdf_mesh_count(const float* tsdf, const int32_t* weight, int nx, int ny, int nz, int min_weight, int64_t* cell_counts, int64_t* quad_counts,
+                       void* stream);
+int fm_tsdf_mesh_emit(const float* tsdf, const int32_t* weight, const float* color, const int32_t* color_weight, int nx, int ny, int nz, float ox,
+                      float oy, float oz, float voxel_size, int min_weight, const int64_t* cell_offsets, const int64_t* quad_offsets, long vertex_rows,
+                      long quad_rows, float* xyz, float* normals, float* rgb, int64_t* cell, int32_t* cell_vertex, int32_t* faces, int64_t* edge,
+                      void* stream);
 
 #ifdef __cplusplus
 }
