@@ -239,10 +239,25 @@ def _dense_flow_is_rough(bwd_flow: Tensor, h: int, w: int) -> bool:
 
     return _derived(bwd_flow, "_fm_dense_rough", (bwd_flow._version, h, w), build)
 
+# the forms of the Procrustes fit's backward, in the order csrc/fm_torch.cpp counts them (FitBackwardForm): the planned backward in one
+# launch / in three, the atomic scatter, the dense fused pass, the dense planned pair, the repeated-batch scatter
+FIT_BACKWARD_FORMS = ("fit_bwd_one_launch", "fit_bwd_three_launch", "fit_bwd_atomic", "fit_bwd_dense_fused", "fit_bwd_dense_planned", "fit_bwd_repeat")
+
+
+class _Counters(dict):
+    """The facades' counters; the FIT_BACKWARD_FORMS entries mirror the operator library's own process-wide counts (the backward runs in
+    C++), read afresh whenever one of them is looked up."""
+
+    def __getitem__(self, key):
+        if key in FIT_BACKWARD_FORMS:
+            self.update(zip(FIT_BACKWARD_FORMS, torch_ops().procrustes_backward_forms()))
+        return super().__getitem__(key)
+
+
 # which backward path the facades selected (tests)
-counters = {"procrustes_planned": 0, "procrustes_dense_planned": 0, "flow_packs": 0, "flow_packs_bitmask": 0, "procrustes_plans_built": 0, "track_tap_samples": 0,
+counters = _Counters({"procrustes_planned": 0, "procrustes_dense_planned": 0, "flow_packs": 0, "flow_packs_bitmask": 0, "procrustes_plans_built": 0, "track_tap_samples": 0,
             "flow_tap_passes": 0, "flow_tap_absorbs": 0, "quat_pose_fwd": 0, "quat_pose_bwd": 0, "flow_residuals": 0, "track_residuals": 0, "alignment_residuals": 0, "focal_sweep": 0,
-            "depth_consistency": 0, "render_views": 0, "voxel_cloud": 0, "tsdf_volume": 0}
+            "depth_consistency": 0, "render_views": 0, "voxel_cloud": 0, "tsdf_volume": 0, **dict.fromkeys(FIT_BACKWARD_FORMS, 0)})
 
 
 class LeadingFrames:

@@ -24,6 +24,7 @@
 #include <torch/custom_class.h>
 #include <torch/library.h>
 
+#include <atomic>
 #include <cmath>
 #include <functional>
 #include <mutex>
@@ -343,6 +344,18 @@ static bool& one_launch_backward_flag() {
 }
 static bool use_one_launch_backward() { return one_launch_backward_flag(); }
 static void set_one_launch_backward(bool on) { one_launch_backward_flag() = on; }
+
+// tests: which form every backward of the Procrustes fit took, counted per process (mirrored into flowmap_amd._ops.counters)
+enum FitBackwardForm { kFitBwdOneLaunch = 0, kFitBwdThreeLaunch, kFitBwdAtomic, kFitBwdDenseFused, kFitBwdDensePlanned, kFitBwdRepeat, kFitBwdForms };
+static std::atomic<int64_t>* fit_backward_counts() {
+  static std::atomic<int64_t> counts[kFitBwdForms] = {};
+  return counts;
+}
+static std::vector<int64_t> procrustes_backward_forms() {
+  std::vector<int64_t> out(kFitBwdForms);
+  for (int i = 0; i < kFitBwdForms; ++i) out[i] = fit_backward_counts()[i].load();
+  return out;
+}
 
 // The root of a step's backward: `loss.backward()` makes autograd fill a fresh ones_like(loss) and hands it down as the seed — one launch — and
 // the flow loss then has to find out ON THE DEVICE that the seed is 1 (fm_scale_if_needed: a second launch that does nothing).  The losses
@@ -747,6 +760,8 @@ struct ProcrustesFit : public Function<ProcrustesFit> {
       }
       if (carried_k.defined() && !add_k) g_k = g_k.defined() ? g_k + carried_k : carried_k;  // (unexpected layout: plain sum)
     }
+    ++fit_backward_counts()[one_launch ? kFitBwdOneLaunch : dense ? (dense_first.defined() ? kFitBwdDensePlanned : kFitBwdDenseFused)
+                            : point_grads.defined() ? kFitBwdThreeLaunch : (rep > 1 && from_depth) ? kFitBwdRepeat : kFitBwdAtomic];
     if (arena_used) g_w = arena->alias();
     if (sink) sink->note_final(g_src);
     if (wsink) {
@@ -1952,6 +1967,7 @@ TORCH_LIBRARY(flowmap_amd, m) {
         fmt::softmin_intrinsics_op);
   m.def("random_subset(int n, int count, Device device, int seed, Tensor? state) -> Tensor", fmt::random_subset);
   m.def("set_one_launch_backward(bool on) -> ()", fmt::set_one_launch_backward);
+  m.def("procrustes_backward_forms() -> int[]", fmt::procrustes_backward_forms);
   m.def("register_unit_seed(Tensor seed) -> ()", fmt::register_unit_seed);
   m.def("unit_seed_uses() -> int", []() { return fmt::unit_seed_uses(); });
   m.def("view_copies() -> int", []() { return fmt::view_copy_counter(); });

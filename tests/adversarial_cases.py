@@ -126,22 +126,27 @@ def case_fit_per_pair(device, cfg):
         d = depth[None].to(device).requires_grad_(True)
         lg = wlogit[None].to(device).requires_grad_(True)
         kk = k.clone().to(device).requires_grad_(True)
-        t_bwd, t_fwd = _ops.ProcrustesFit.apply(d, kk, None, lg, bwd, idx, 100.0, 1)
+        # the chained fit (without the extrinsics): only it leaves the records the one-launch backward reads
+        t_bwd, t_fwd, _ = _ops.ProcrustesFit.apply_chained(d, kk, None, lg, bwd, idx, 100.0, 1, chain=True, want_extrinsics=False)
         ((t_bwd + 0.5 * t_fwd) * cot_d).sum().backward()
         return {"t_bwd": t_bwd.detach().cpu(), "g_depth": d.grad[0].cpu(), "g_logits": lg.grad[0].cpu(), "g_k": kk.grad[0].cpu()}
 
+    def forms():
+        return tuple(_ops.counters[name] for name in ("fit_bwd_one_launch", "fit_bwd_three_launch", "fit_bwd_atomic"))
+
     before = _ops.counters["procrustes_planned"]
+    one, three_, atomic = forms()
     runs = {"atomics": run()}
-    assert _ops.counters["procrustes_planned"] == before
+    assert _ops.counters["procrustes_planned"] == before and forms() == (one, three_, atomic + 1)
     run()  # builds the plan
     runs["planned"] = run()
-    assert _ops.counters["procrustes_planned"] == before + 2
+    assert _ops.counters["procrustes_planned"] == before + 2 and forms() == (one + 2, three_, atomic + 1)
     torch_ops().set_one_launch_backward(False)
     try:
         runs["three-launch"] = run()
     finally:
         torch_ops().set_one_launch_backward(True)
-    assert _ops.counters["procrustes_planned"] == before + 3
+    assert _ops.counters["procrustes_planned"] == before + 3 and forms() == (one + 2, three_ + 1, atomic + 1)  # two different paths
 
     tag = f"fit {f}x{h}x{w}-P{points}-s{seed}"
     for name, got in runs.items():

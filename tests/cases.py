@@ -215,17 +215,22 @@ def case_procrustes_planned_backward(dev):
         d = depth[None].to(dev).requires_grad_(True)
         lg = wlogit[None].to(dev).requires_grad_(True)
         kk = k.clone().requires_grad_(True)
-        t_bwd, t_fwd = _ops.ProcrustesFit.apply(d, kk, None, lg, bwd, indices, 100.0, 1)
+        # the chained fit (without the extrinsics): only it leaves the records the one-launch backward reads
+        t_bwd, t_fwd, _ = _ops.ProcrustesFit.apply_chained(d, kk, None, lg, bwd, indices, 100.0, 1, chain=True, want_extrinsics=False)
         ((t_bwd + 0.5 * t_fwd) * cot).sum().backward()
         return d.grad, lg.grad, kk.grad
 
+    def forms():
+        return tuple(_ops.counters[name] for name in ("fit_bwd_one_launch", "fit_bwd_three_launch", "fit_bwd_atomic"))
+
     idx = torch.linspace(0, h * w - 1, points).to(torch.int64).to(dev)
     before = _ops.counters["procrustes_planned"]
+    one, three_, atomic = forms()
     first = run(idx)  # atomics (first sighting)
-    assert _ops.counters["procrustes_planned"] == before
+    assert _ops.counters["procrustes_planned"] == before and forms() == (one, three_, atomic + 1)
     second = run(idx)  # builds the plan
     third = run(idx)
-    assert _ops.counters["procrustes_planned"] == before + 2
+    assert _ops.counters["procrustes_planned"] == before + 2 and forms() == (one + 2, three_, atomic + 1)
     for a, b_, c, name in zip(first, second, third, ("g_depth", "g_logits", "g_k")):
         assert_close(b_, a, 2e-5, abs_=1e-7, what=f"planned vs atomic {name}")
         # planned steps have no float atomics on the big tensors (the small fp64 block sums before them
@@ -240,7 +245,7 @@ def case_procrustes_planned_backward(dev):
         three = run(idx)
     finally:
         torch_ops().set_one_launch_backward(True)
-    assert _ops.counters["procrustes_planned"] == before + 3
+    assert _ops.counters["procrustes_planned"] == before + 3 and forms() == (one + 2, three_ + 1, atomic + 1)  # two different paths
     for c, t3, name in zip(third, three, ("g_depth", "g_logits", "g_k")):
         assert_close(c, t3, 1e-6, abs_=1e-9, what=f"one launch vs three {name}")
     before += 1
@@ -251,7 +256,7 @@ def case_procrustes_planned_backward(dev):
     assert _ops.counters["procrustes_planned"] == before + 2  # duplicates: atomics every time
     for _ in range(3):
         run(idx.clone())  # a new index tensor each step (randomize_points): never planned
-    assert _ops.counters["procrustes_planned"] == before + 2
+    assert _ops.counters["procrustes_planned"] == before + 2 and forms() == (one + 2, three_ + 1, atomic + 7)
     assert got[0].isfinite().all()
 
 

@@ -194,7 +194,7 @@ def test_tracking_scene_vs_oracle_fp64():
     compare(ours, ref, masks=step_masks((h, w), 300, sc["flows"], tr))  # consistent scene: 1e-4 outright, dL/dfocal included
 
 
-@pytest.mark.parametrize("steps", [1, 5, 149, 700])
+@pytest.mark.parametrize("steps", [1, 5, 149, 255, 256, 257, 511, 513, 700])  # (255 .. 513: the 256 threads of the chain, chunks of 1, 2 and 3 steps)
 def test_pose_chain_scan_matches_serial_oracle(steps):
     """The parallel-scan pose chain (chunks + Hillis-Steele in LDS, additive suffix scan
     in the backward) against the oracle's serial fp64 loop, incl. chunk sizes > 1."""
