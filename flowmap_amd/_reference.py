@@ -27,10 +27,10 @@ counters = {"host_calls": 0}
 def _first_tensor(obj, depth: int = 0) -> Optional[torch.Tensor]:
     if torch.is_tensor(obj):
         return obj
-    lazy = getattr(type(obj), "_fm_lazy", None)  # LazyWeights / LazyExtrinsics: any other attribute read would EVALUATE what they stand for
+    lazy = getattr(type(obj), "_fm_lazy", None)  # LazySurfaces / LazyWeights / LazyExtrinsics: any other attribute read could EVALUATE what they stand for
     if lazy:
         return obj.__dict__[lazy]
-    depths = getattr(obj, "depths", None)  # LazySurfaces, BackboneOutput, ModelOutput
+    depths = getattr(obj, "depths", None)  # BackboneOutput, ModelOutput
     if torch.is_tensor(depths):
         return depths
     videos = getattr(obj, "videos", None)  # Batch
@@ -62,10 +62,10 @@ def on_host(*objs) -> bool:
     for obj in objs:
         if isinstance(obj, _Tensor):
             return obj.device.type == "cpu"
-        lazy = getattr(type(obj), "_fm_lazy", None)  # LazyWeights / LazyExtrinsics (see _first_tensor)
+        lazy = getattr(type(obj), "_fm_lazy", None)  # LazySurfaces / LazyWeights / LazyExtrinsics (see _first_tensor)
         if lazy:
             return obj.__dict__[lazy].device.type == "cpu"
-        t = getattr(obj, "depths", None)  # LazySurfaces, BackboneOutput, ModelOutput
+        t = getattr(obj, "depths", None)  # BackboneOutput, ModelOutput
         if not isinstance(t, _Tensor):
             t = getattr(obj, "videos", None)  # Batch
         if not isinstance(t, _Tensor):

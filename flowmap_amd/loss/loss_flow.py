@@ -11,7 +11,7 @@ from torch import Tensor
 from .. import _ops, _reference
 from .._base import parse_window
 from ..types import FlowResiduals
-from ..model.projection import LazyExtrinsics, LazySurfaces, _dense_extrinsics, compute_backward_flow, compute_forward_flow, sample_image_grid
+from ..model.projection import LazyExtrinsics, LazySurfaces, _dense_extrinsics, _peek_extrinsics, compute_backward_flow, compute_forward_flow, sample_image_grid
 from .loss import Loss, LossCfgCommon, or_one
 from .mapping import MappingCfg, get_mapping
 
@@ -155,9 +155,7 @@ class LossFlow(Loss[LossFlowCfg]):
         forward_flow = _reference.host_twin("compute_forward_flow", batch) or compute_forward_flow
         backward_flow = _reference.host_twin("compute_backward_flow", batch) or compute_backward_flow
         xy, _ = grid((h, w), batch.videos.device)
-        ext = model_output.extrinsics
-        if isinstance(ext, LazyExtrinsics):  # the chain for this call only: nothing is noted on the flow tensor
-            ext = ext._dense if ext._dense is not None else _ops.PoseChain.apply(ext._rel)
+        ext = _peek_extrinsics(model_output.extrinsics)  # (a LazyExtrinsics: the chain for this call only, nothing is noted on the flow tensor)
         win, frames = slice(first, first + count), slice(first, first + count + 1)
         surfaces, ext, k = model_output.surfaces[:, frames], ext[:, frames], model_output.intrinsics[:, frames]
         fields = []

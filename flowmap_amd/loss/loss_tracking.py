@@ -13,7 +13,7 @@ import torch
 from .. import _ops, _reference
 from .._base import parse_window
 from ..types import TrackResiduals
-from ..model.projection import LazySurfaces, _dense_extrinsics, compute_track_flow
+from ..model.projection import LazySurfaces, _dense_extrinsics, _peek_extrinsics, compute_track_flow
 from .loss import Loss, LossCfgCommon, or_one
 from .mapping import MappingCfg, get_mapping
 
@@ -133,7 +133,7 @@ class LossTracking(Loss[LossTrackingCfg]):
 
     def _residuals_fused(self, tracks, model_output, first: int, count: int, predicted: bool, sums: bool) -> list:
         s: LazySurfaces = model_output.surfaces
-        ext = _dense_extrinsics(model_output.extrinsics).detach()
+        ext = _peek_extrinsics(model_output.extrinsics)  # (a LazyExtrinsics: the chain for this call only — it stays unevaluated, no note on the flows)
         if s.depths.shape[1] != ext.shape[1]:
             raise RuntimeError(f"flowmap_amd: LossTracking.residuals needs every frame's depth on this device (depth holds {s.depths.shape[1]} of "
                                f"{ext.shape[1]} frames: a frame shard)")

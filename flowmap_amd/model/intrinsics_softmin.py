@@ -119,24 +119,18 @@ class IntrinsicsSoftmin(nn.Module):
             # ---- per-candidate Procrustes fit of frames (0, 1), images read in place -----------
             depths = _ops.LeadingFrames.apply(backbone_output.depths, 2)
             _ops.note_leading_frames(backbone_output.depths, 2)  # random pixels of frames 0 / 1: an in-pass depth update skips both frames
-            weights = backbone_output.weights
-            sens = 0.0
-            if isinstance(weights, LazyWeights):
-                weights_01, sens = _ops.LeadingFrames.apply(weights.logits, 1), weights.sensitivity
-            else:
-                weights_01 = _ops.LeadingFrames.apply(weights, 1)
+            weights, sens = backbone_output.weights, 0.0
+            if isinstance(weights, LazyWeights):  # its logits; at sensitivity 0, which cannot be folded into the kernels, its value
+                weights, sens = weights.kernel_input(keep=True)
+            weights_01 = _ops.LeadingFrames.apply(weights, 1)
             rel, _ = _ops.ProcrustesFit.apply(depths, k_pair, None, weights_01, bwd_01, idx, sens, n)  # (b*n,1,4,4): frame 1 -> frame 0
 
             # ---- pose-induced backward flow error per candidate (intrinsics_softmin.py:105-121): one
             # launch reads the sampled pixels' depth / weight / flow straight from the images
-            if sens != 0.0 or not isinstance(weights, LazyWeights):
-                score_weights, score_sens = weights_01, sens
-            else:  # a LazyWeights with sensitivity 0 cannot be folded into the kernel
-                score_weights, score_sens = _ops.LeadingFrames.apply(weights.materialize(), 1), 0.0
             # ... reduced to the softmin weights, the blended K of every frame and its inverse
             # (intrinsics_softmin.py:123-141).  The reference returns K as an expanded view; here it is
             # materialised once and every consumer of the step reads this tensor.
-            return _ops.softmin_intrinsics(depths, score_weights, bwd_01, idx, candidate_k, rel.reshape(b * n, 4, 4), score_sens, f)
+            return _ops.softmin_intrinsics(depths, weights_01, bwd_01, idx, candidate_k, rel.reshape(b * n, 4, 4), sens, f)
 
         if self.shard is not None and self.shard.active:  # frames (0, 1) of the VIDEO live on rank 0
             intrinsics, soft = self.shard.softmin_from_rank0(sweep, b, n, f, device)

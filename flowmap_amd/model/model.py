@@ -20,7 +20,7 @@ from ..types import ModelOutput
 from .backbone import BackboneExplicitDepth, BackboneExplicitDepthCfg  # noqa: F401  (flowmap/model/backbone/backbone_explicit_depth.py)
 from .extrinsics_procrustes import ExtrinsicsProcrustes, ExtrinsicsProcrustesCfg
 from .extrinsics_regressed import ExtrinsicsRegressed, ExtrinsicsRegressedCfg
-from .projection import depth_consistency, render_views, sample_image_grid, unproject
+from .projection import _peek_extrinsics, depth_consistency, render_views, sample_image_grid, unproject
 
 
 _K_CONSTANTS: dict = {}
@@ -140,30 +140,22 @@ class Model(nn.Module):
         """export.voxel_point_cloud of batch entry ``entry`` of a ModelOutput's depths under its intrinsics and extrinsics, coloured with
         ``batch.videos`` when a batch is given (``voxel_size``, ``keep`` (F,H,W), ``min_count``, ``capacity``, ``details`` as there)
         -> VoxelCloud.  It only reads: a LazyExtrinsics stays unevaluated."""
-        from .. import _ops
         from ..export import voxel_point_cloud
-        from .projection import LazyExtrinsics
 
         if voxel_size is None:
             raise ValueError("flowmap_amd: Model.point_cloud: voxel_size is required")
-        ext = model_output.extrinsics
-        if isinstance(ext, LazyExtrinsics):  # the chain for this call only: nothing is kept on the LazyExtrinsics
-            ext = ext._dense if ext._dense is not None else _ops.PoseChain.apply(ext._rel.detach())
+        ext = _peek_extrinsics(model_output.extrinsics)  # (a LazyExtrinsics: the chain for this call only, nothing is kept on it)
         colors = None if batch is None else batch.videos[entry]
-        return voxel_point_cloud(model_output.depths[entry].detach(), model_output.intrinsics[entry].detach(), ext[entry].detach(), colors, voxel_size, **kw)
+        return voxel_point_cloud(model_output.depths[entry].detach(), model_output.intrinsics[entry].detach(), ext[entry], colors, voxel_size, **kw)
 
     def tsdf(self, model_output, batch=None, voxel_size=None, entry=0, **kw):
         """export.tsdf_volume of batch entry ``entry`` of a ModelOutput's depths under its intrinsics and extrinsics, coloured with
         ``batch.videos`` when a batch is given (``voxel_size``, ``origin``, ``dims``, ``truncation``, ``near``, ``keep`` (F,H,W), ``frames``
         as there) -> TsdfVolume.  It only reads: a LazyExtrinsics stays unevaluated."""
-        from .. import _ops
         from ..export import tsdf_volume
-        from .projection import LazyExtrinsics
 
         if voxel_size is None:
             raise ValueError("flowmap_amd: Model.tsdf: voxel_size is required")
-        ext = model_output.extrinsics
-        if isinstance(ext, LazyExtrinsics):  # the chain for this call only: nothing is kept on the LazyExtrinsics
-            ext = ext._dense if ext._dense is not None else _ops.PoseChain.apply(ext._rel.detach())
+        ext = _peek_extrinsics(model_output.extrinsics)  # (a LazyExtrinsics: the chain for this call only, nothing is kept on it)
         colors = None if batch is None else batch.videos[entry]
-        return tsdf_volume(model_output.depths[entry].detach(), model_output.intrinsics[entry].detach(), ext[entry].detach(), colors, voxel_size, **kw)
+        return tsdf_volume(model_output.depths[entry].detach(), model_output.intrinsics[entry].detach(), ext[entry], colors, voxel_size, **kw)

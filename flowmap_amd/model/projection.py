@@ -93,55 +93,57 @@ def lazy_surfaces_enabled() -> bool:
     return _LAZY
 
 
-class LazySurfaces:
-    """Camera-space surfaces defined by (depths, intrinsics) but not stored.
+class _LazyValue:
+    """What the values that are not stored (LazySurfaces, LazyWeights, LazyExtrinsics) share — the tensor protocol, stated once.
 
-    Quacks like the (b, f, h, w, 3) tensor for what the hot path's callers read
-    (``shape``, ``device``, ``dtype``, ``ndim``, frame slicing ``[:, s:e]``); any other
-    use transparently materialises the real tensor (with autograd intact).
-    """
+    A subclass names its source tensor in ``_fm_lazy`` (``device`` and ``dtype`` are that tensor's, and flowmap_amd/_reference.py asks a
+    lazy value for its device through this attribute, without evaluating it), gives its ``shape`` and says in ``_evaluate`` how the value
+    is computed.  Metadata never evaluates.  Any other use — an attribute, an index, a torch function — behaves like the real tensor:
+    ``materialize()`` evaluates once (autograd intact) and keeps the result in ``_dense``.  ``peek()`` is the read-only door."""
 
-    def __init__(self, depths: Tensor, intrinsics: Tensor):
-        self.depths = depths  # (b, f, h, w)
-        self.intrinsics = intrinsics  # (b, f, 3, 3)
-        self._dense: Optional[Tensor] = None
+    _fm_lazy = ""
+    _dense: Optional[Tensor] = None
 
     # -- cheap metadata ---------------------------------------------------------------
     @property
-    def shape(self):
-        return torch.Size((*self.depths.shape, 3))
-
-    @property
     def device(self):
-        return self.depths.device
+        return self.__dict__[self._fm_lazy].device
 
     @property
     def dtype(self):
-        return self.depths.dtype
+        return self.__dict__[self._fm_lazy].dtype
 
     @property
     def ndim(self):
-        return 5
+        return len(self.shape)
 
     def dim(self):
-        return 5
+        return len(self.shape)
 
     def size(self, i=None):
         return self.shape if i is None else self.shape[i]
 
-    # -- materialisation ----------------------------------------------------------------
+    # -- the value --------------------------------------------------------------------
+    def _evaluate(self, detached: bool) -> Tensor:
+        """The value from the sources; ``detached``: from the detached sources, and without any side effect."""
+        raise NotImplementedError
+
     def materialize(self) -> Tensor:
         if self._dense is None:
-            b, f, h, w = self.depths.shape
-            xy, _ = sample_image_grid((h, w), self.depths.device)
-            self._dense = _unproject_dense(xy, self.depths, self.intrinsics.reshape(b, f, 1, 1, 3, 3))
+            self._dense = self._evaluate(False)
         return self._dense
 
+    def peek(self) -> Tensor:
+        """The value for this call only, detached: the evaluated one if there is one, otherwise computed from the detached sources —
+        nothing is kept on this object and no note is left on any tensor.  What the diagnostics that "only read" use."""
+        return (self._dense if self._dense is not None else self._evaluate(True)).detach()
+
+    @staticmethod
+    def _frame_slice(item) -> bool:
+        """``[:, s:e]``: the index that LazySurfaces and LazyWeights answer without evaluating."""
+        return isinstance(item, tuple) and len(item) == 2 and isinstance(item[0], slice) and item[0] == slice(None) and isinstance(item[1], slice)
+
     def __getitem__(self, item):
-        # frame slices keep laziness: surfaces[:, s:e]  (loss_tracking.py:48-49)
-        if (isinstance(item, tuple) and len(item) == 2 and isinstance(item[0], slice) and item[0] == slice(None)
-                and isinstance(item[1], slice)):
-            return LazySurfaces(self.depths[item], self.intrinsics[item])
         return self.materialize()[item]
 
     def __getattr__(self, name):
@@ -152,11 +154,39 @@ class LazySurfaces:
 
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
-        kwargs = kwargs or {}
-        conv = lambda a: a.materialize() if isinstance(a, LazySurfaces) else a  # noqa: E731
-        args = tuple(conv(a) for a in args)
-        kwargs = {k: conv(v) for k, v in kwargs.items()}
-        return func(*args, **kwargs)
+        conv = lambda a: a.materialize() if isinstance(a, _LazyValue) else a  # noqa: E731  (top-level arguments only)
+        return func(*(conv(a) for a in args), **{k: conv(v) for k, v in (kwargs or {}).items()})
+
+
+class LazySurfaces(_LazyValue):
+    """Camera-space surfaces defined by (depths, intrinsics) but not stored.
+
+    Quacks like the (b, f, h, w, 3) tensor for what the hot path's callers read
+    (``shape``, ``device``, ``dtype``, ``ndim``, frame slicing ``[:, s:e]``); any other
+    use transparently materialises the real tensor (with autograd intact).
+    """
+
+    _fm_lazy = "depths"
+
+    def __init__(self, depths: Tensor, intrinsics: Tensor):
+        self.depths = depths  # (b, f, h, w)
+        self.intrinsics = intrinsics  # (b, f, 3, 3)
+
+    @property
+    def shape(self):
+        return torch.Size((*self.depths.shape, 3))
+
+    def _evaluate(self, detached: bool) -> Tensor:
+        depths, intrinsics = (self.depths.detach(), self.intrinsics.detach()) if detached else (self.depths, self.intrinsics)
+        b, f, h, w = depths.shape
+        xy, _ = sample_image_grid((h, w), depths.device)
+        return _unproject_dense(xy, depths, intrinsics.reshape(b, f, 1, 1, 3, 3))
+
+    def __getitem__(self, item):
+        # frame slices keep laziness: surfaces[:, s:e]  (loss_tracking.py:48-49)
+        if self._frame_slice(item):
+            return LazySurfaces(self.depths[item], self.intrinsics[item])
+        return self.materialize()[item]
 
     def __repr__(self):
         return f"LazySurfaces(shape={tuple(self.shape)}, device={self.device})"
@@ -166,14 +196,14 @@ def _dense(surfaces) -> Tensor:
     return surfaces.materialize() if isinstance(surfaces, LazySurfaces) else surfaces
 
 
-class LazyWeights:
+class LazyWeights(_LazyValue):
     """Correspondence weights sigmoid(sensitivity · logits) (BackboneExplicitDepth,
     flowmap/model/backbone/backbone_explicit_depth.py:38-41) that are not stored: only
     the P sampled pixels per pair are ever read (0.1 % at 720p with P = 1000), so
     ``align_surfaces`` applies the sigmoid inside its gather and writes the logit gradient
     directly.  Any other use materialises the real (b, f-1, h, w) tensor."""
 
-    _fm_lazy = "logits"  # (flowmap_amd/_reference.py asks a lazy value for its device through this attribute, without evaluating it)
+    _fm_lazy = "logits"
 
     def __init__(self, logits: Tensor, sensitivity: float, lazy_slices: bool = True):
         self.logits = logits  # (b, f-1, h, w)
@@ -181,64 +211,43 @@ class LazyWeights:
         # frame slices stay lazy only for consumers that understand a LazyWeights (this package's IntrinsicsSoftmin / align_surfaces); the
         # reference's own IntrinsicsSoftmin hands `weights[:, :1]` to einops (intrinsics_softmin.py:120), which needs a real tensor
         self.lazy_slices = bool(lazy_slices)
-        self._dense: Optional[Tensor] = None
 
     @property
     def shape(self):
         return self.logits.shape
 
-    @property
-    def device(self):
-        return self.logits.device
+    def _evaluate(self, detached: bool) -> Tensor:
+        return (self.sensitivity * (self.logits.detach() if detached else self.logits)).sigmoid()
 
-    @property
-    def dtype(self):
-        return self.logits.dtype
-
-    def materialize(self) -> Tensor:
-        if self._dense is None:
-            self._dense = (self.sensitivity * self.logits).sigmoid()
-        return self._dense
-
-    @property
-    def ndim(self):
-        return self.logits.ndim
-
-    def dim(self):
-        return self.logits.dim()
-
-    def size(self, i=None):
-        return self.logits.shape if i is None else self.logits.shape[i]
+    def kernel_input(self, keep: bool = False):
+        """(the tensor the kernels read, sensitivity): the logits, which the kernels put through the sigmoid themselves, when the
+        sensitivity is not 0; at sensitivity 0, which the kernels read as "these are the weights", the value — ``peek()`` for the callers
+        that only read, ``materialize()`` (differentiable, kept) with ``keep``, for a training step."""
+        if self.sensitivity != 0.0:
+            return self.logits, self.sensitivity
+        return (self.materialize() if keep else self.peek()), 0.0
 
     def __getitem__(self, item):
         # frame slices keep laziness: weights[:, :1]  (intrinsics_softmin.py:100,120 read the first pair only)
-        if (isinstance(item, tuple) and len(item) == 2 and isinstance(item[0], slice) and item[0] == slice(None)
-                and isinstance(item[1], slice)):
+        if self._frame_slice(item):
             if self.lazy_slices:
                 return LazyWeights(self.logits[item], self.sensitivity)
             if self._dense is None:  # the sigmoid of the frames asked for, not of the whole (b, f-1, h, w) tensor
                 return (self.sensitivity * self.logits[item]).sigmoid()
         return self.materialize()[item]
 
-    def __getattr__(self, name):
-        if name.startswith("_"):
-            raise AttributeError(name)
-        return getattr(self.materialize(), name)
-
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
-        kwargs = kwargs or {}
         if func in (torch.ones_like, torch.zeros_like, torch.empty_like) and args and isinstance(args[0], LazyWeights):
             # model/model.py:67-68 (`use_correspondence_weights: false`) asks for the shape only: no sigmoid over (f-1, h, w) for that
-            return func(args[0].logits.detach(), *args[1:], **kwargs)
-        conv = lambda a: a.materialize() if isinstance(a, (LazyWeights, LazySurfaces)) else a  # noqa: E731
-        return func(*tuple(conv(a) for a in args), **{k: conv(v) for k, v in kwargs.items()})
+            return func(args[0].logits.detach(), *args[1:], **(kwargs or {}))
+        return super().__torch_function__(func, types, args, kwargs)
 
     def __repr__(self):
         return f"LazyWeights(shape={tuple(self.shape)}, sensitivity={self.sensitivity})"
 
 
-class LazyExtrinsics:
+class LazyExtrinsics(_LazyValue):
     """The camera-to-world chain of ``get_extrinsics`` (flowmap/model/projection.py:187-210) over the fit's relative poses, NOT evaluated yet.
 
     ``align_surfaces`` returns one while gradients are being recorded (a training step) and nothing has asked for the chain in an earlier
@@ -246,50 +255,30 @@ class LazyExtrinsics:
     that is the LAST block's one wave working for ~7 us at 149 poses while the rest of the GPU waits (``profiles/r06_fit_microbench.jsonl``).
     Anything else — an attribute, an index, a torch function, this package's tracking loss — evaluates the chain (one launch,
     ``fm_pose_chain_fwd``, differentiable through the fit's poses) and notes on the constant flow tensor that the chain is wanted: from the
-    next step on the fit's own launch produces it again, as in rounds 1-5.  Under ``torch.no_grad()`` (validation, ``Model.export``: the
-    reference's ``ModelExports`` checks its fields) the module returns the tensor as before; so does the function-level ``align_surfaces``."""
+    next step on the fit's own launch produces it again, as in rounds 1-5.  The diagnostics that only read take ``peek()``, which does
+    neither.  Under ``torch.no_grad()`` (validation, ``Model.export``: the reference's ``ModelExports`` checks its fields) the module
+    returns the tensor as before; so does the function-level ``align_surfaces``."""
 
-    _fm_lazy = "_rel"  # (flowmap_amd/_reference.py asks a lazy value for its device through this attribute, without evaluating it)
+    _fm_lazy = "_rel"
 
     def __init__(self, rel: Tensor, rel_inv: Tensor, flow_tensor: Optional[Tensor] = None):
         self._rel = rel  # (b, f-1, 4, 4): later camera -> earlier camera, the factors of the chain
         self._fm_relative_poses = (rel_inv, rel)
         self._flow_tensor = flow_tensor
-        self._dense: Optional[Tensor] = None
 
     @property
     def shape(self):
         b, pairs = self._rel.shape[:2]
         return torch.Size((b, pairs + 1, 4, 4))
 
-    @property
-    def device(self):
-        return self._rel.device
-
-    @property
-    def dtype(self):
-        return self._rel.dtype
-
-    @property
-    def ndim(self):
-        return 4
-
-    def dim(self):
-        return 4
-
-    def size(self, i=None):
-        return self.shape if i is None else self.shape[i]
-
-    def materialize(self) -> Tensor:
-        if self._dense is None:
-            self._dense = _ops.PoseChain.apply(self._rel)
-            self._dense._fm_relative_poses = self._fm_relative_poses
-            if self._flow_tensor is not None:  # something reads the chain in this optimisation: the fit's launch chains it from the next step on
-                self._flow_tensor.__dict__["_fm_extrinsics_wanted"] = True
-        return self._dense
-
-    def __getitem__(self, item):
-        return self.materialize()[item]
+    def _evaluate(self, detached: bool) -> Tensor:
+        if detached:
+            return _ops.PoseChain.apply(self._rel.detach())
+        dense = _ops.PoseChain.apply(self._rel)
+        dense._fm_relative_poses = self._fm_relative_poses
+        if self._flow_tensor is not None:  # something reads the chain in this optimisation: the fit's launch chains it from the next step on
+            self._flow_tensor.__dict__["_fm_extrinsics_wanted"] = True
+        return dense
 
     def __len__(self):
         return int(self._rel.shape[0])
@@ -315,23 +304,17 @@ class LazyExtrinsics:
     def __deepcopy__(self, memo):
         return self.materialize().detach().clone()
 
-    def __getattr__(self, name):
-        if name.startswith("_"):
-            raise AttributeError(name)
-        return getattr(self.materialize(), name)
-
-    @classmethod
-    def __torch_function__(cls, func, types, args=(), kwargs=None):
-        kwargs = kwargs or {}
-        conv = lambda a: a.materialize() if isinstance(a, (LazyExtrinsics, LazyWeights, LazySurfaces)) else a  # noqa: E731
-        return func(*tuple(conv(a) for a in args), **{k: conv(v) for k, v in kwargs.items()})
-
     def __repr__(self):
         return f"LazyExtrinsics(shape={tuple(self.shape)}, device={self.device}, evaluated={self._dense is not None})"
 
 
 def _dense_extrinsics(extrinsics):
     return extrinsics.materialize() if isinstance(extrinsics, LazyExtrinsics) else extrinsics
+
+
+def _peek_extrinsics(extrinsics) -> Tensor:
+    """The extrinsics for this call only, detached: a tensor as it is, a LazyExtrinsics through ``peek()`` — it stays unevaluated."""
+    return extrinsics.peek() if isinstance(extrinsics, _LazyValue) else extrinsics.detach()
 
 
 # --------------------------------------------------------------------------------------
@@ -560,14 +543,36 @@ def _check_indices(what: str, indices, dev) -> None:
         raise RuntimeError(f"flowmap_amd: {what}: indices must be a non-empty 1-D tensor (got shape {tuple(indices.shape)})")
 
 
+def _check_posed_depths(what: str, depths, intrinsics, extrinsics, colors=None) -> Tensor:
+    """The shapes depth_consistency and render_views ask of ``depths`` (b, f, h, w), ``intrinsics`` (b, f, 3, 3), ``extrinsics`` (b, f, 4, 4)
+    — a tensor or a LazyExtrinsics — and ``colors`` (b, f, 3, h, w) or None.  -> the tensor that stands for the extrinsics where a dtype
+    or a device is asked (a LazyExtrinsics' relative poses: it is not evaluated)."""
+    pose_tensor = extrinsics._rel if isinstance(extrinsics, LazyExtrinsics) else extrinsics
+    if not torch.is_tensor(depths) or not torch.is_tensor(intrinsics) or not torch.is_tensor(pose_tensor):
+        raise RuntimeError(f"flowmap_amd: {what}: depths and intrinsics must be tensors, extrinsics a tensor or a LazyExtrinsics")
+    if depths.dim() != 4:
+        raise RuntimeError(f"flowmap_amd: {what}: depths of shape {tuple(depths.shape)}; expected (batch, frame, height, width)")
+    b, f, h, w = depths.shape
+    if tuple(intrinsics.shape) != (b, f, 3, 3):
+        raise RuntimeError(f"flowmap_amd: {what}: intrinsics of shape {tuple(intrinsics.shape)} do not match the depths {(b, f, h, w)}: expected {(b, f, 3, 3)}")
+    if tuple(extrinsics.shape) != (b, f, 4, 4):
+        raise RuntimeError(f"flowmap_amd: {what}: extrinsics of shape {tuple(extrinsics.shape)} do not match the depths {(b, f, h, w)}: expected {(b, f, 4, 4)}")
+    if colors is not None and (not torch.is_tensor(colors) or tuple(colors.shape) != (b, f, 3, h, w)):
+        raise RuntimeError(f"flowmap_amd: {what}: colors of shape {tuple(getattr(colors, 'shape', ()))} do not match the depths {(b, f, h, w)}: "
+                           f"expected {(b, f, 3, h, w)}")
+    return pose_tensor
+
+
+def _check_float32(what: str, named) -> None:
+    for name, value in named:
+        if value.dtype != torch.float32:
+            raise RuntimeError(f"flowmap_amd: {what}: {name} must be float32 (got {value.dtype})")
+
+
 def _peek_weights(weights):
-    """(what the kernel reads, sensitivity) of a weights argument WITHOUT evaluating a LazyWeights: its logits and sensitivity, or — at
-    sensitivity 0 — its value, not kept on the object; a tensor (or None) as it is, with sensitivity 0."""
-    if not isinstance(weights, LazyWeights):
-        return weights, 0.0
-    if weights.sensitivity != 0.0:
-        return weights.logits, weights.sensitivity
-    return (weights._dense if weights._dense is not None else (0.0 * weights.logits).sigmoid()), 0.0
+    """(what the kernel reads, sensitivity) of a weights argument WITHOUT evaluating a LazyWeights (``LazyWeights.kernel_input``); a
+    tensor (or None) as it is, with sensitivity 0."""
+    return weights.kernel_input() if isinstance(weights, LazyWeights) else (weights, 0.0)
 
 
 def alignment_residuals(surfaces, backward_flows: Tensor, backward_weights, extrinsics, indices: Optional[Tensor] = None, pairs=None,
@@ -614,10 +619,7 @@ def alignment_residuals(surfaces, backward_flows: Tensor, backward_weights, extr
         if direct is not None and tuple(direct[1].shape) == (b, f - 1, 4, 4):
             rel = direct[1].detach()
         else:
-            ext = extrinsics
-            if isinstance(ext, LazyExtrinsics):  # the chain for this call only: nothing is noted on the flow tensor
-                ext = ext._dense if ext._dense is not None else _ops.PoseChain.apply(ext._rel.detach())
-            rel = _ops.RelativePoses.apply(ext.detach())[1]
+            rel = _ops.RelativePoses.apply(_peek_extrinsics(extrinsics))[1]  # (a LazyExtrinsics: the chain for this call only)
 
         backward_weights, sens = _peek_weights(backward_weights)
         if backward_weights is not None:
@@ -703,22 +705,9 @@ def depth_consistency(depths: Tensor, intrinsics: Tensor, extrinsics, offsets=(-
     noted on any tensor, no LazyExtrinsics is left evaluated, no look-ahead, tap image or optimiser state moves.  Host tensors after
     install() go to the same composition of the reference's own functions; without install() they are refused."""
     with torch.no_grad():
-        lazy = isinstance(extrinsics, LazyExtrinsics)
-        pose_tensor = extrinsics._rel if lazy else extrinsics
-        if not torch.is_tensor(depths) or not torch.is_tensor(intrinsics) or not torch.is_tensor(pose_tensor):
-            raise RuntimeError("flowmap_amd: depth_consistency: depths and intrinsics must be tensors, extrinsics a tensor or a LazyExtrinsics")
-        if depths.dim() != 4:
-            raise RuntimeError(f"flowmap_amd: depth_consistency: depths of shape {tuple(depths.shape)}; expected (batch, frame, height, width)")
+        pose_tensor = _check_posed_depths("depth_consistency", depths, intrinsics, extrinsics)
         b, f, h, w = depths.shape
-        if tuple(intrinsics.shape) != (b, f, 3, 3):
-            raise RuntimeError(f"flowmap_amd: depth_consistency: intrinsics of shape {tuple(intrinsics.shape)} do not match the depths {(b, f, h, w)}: "
-                               f"expected {(b, f, 3, 3)}")
-        if tuple(extrinsics.shape) != (b, f, 4, 4):
-            raise RuntimeError(f"flowmap_amd: depth_consistency: extrinsics of shape {tuple(extrinsics.shape)} do not match the depths {(b, f, h, w)}: "
-                               f"expected {(b, f, 4, 4)}")
-        for name, value in (("depths", depths), ("intrinsics", intrinsics), ("extrinsics", pose_tensor)):
-            if value.dtype != torch.float32:
-                raise RuntimeError(f"flowmap_amd: depth_consistency: {name} must be float32 (got {value.dtype})")
+        _check_float32("depth_consistency", (("depths", depths), ("intrinsics", intrinsics), ("extrinsics", pose_tensor)))
         if f < 2:
             raise ValueError("flowmap_amd: depth_consistency: a video of one frame has no other frame to compare with")
         offsets = _check_offsets(offsets, f)
@@ -733,16 +722,14 @@ def depth_consistency(depths: Tensor, intrinsics: Tensor, extrinsics, offsets=(-
 
         if _reference.twins and _reference.on_host(depths):  # host tensors after install(): the reference's own functions
             _reference.counters["host_calls"] += 1
-            ext = extrinsics.materialize().detach() if lazy else extrinsics.detach()  # (a LazyExtrinsics of host tensors is the reference's own)
+            ext = _dense_extrinsics(extrinsics).detach()  # (a LazyExtrinsics of host tensors is the reference's own)
             return _consistency_on_host(_reference.twins.__getitem__, depths.detach(), intrinsics.detach(), ext, offsets, first, count,
                                         None if tolerance is None else float(tolerance), details, sums)
         _refuse_host("depth_consistency", dev)
         check_device(depths, intrinsics, pose_tensor)
-        ext = extrinsics
-        if lazy:  # the chain for this call only: nothing is kept on the LazyExtrinsics or noted on the flow tensor
-            ext = ext._dense if ext._dense is not None else _ops.PoseChain.apply(ext._rel.detach())
+        ext = _peek_extrinsics(extrinsics)  # (a LazyExtrinsics: the chain for this call only, nothing kept on it or noted on the flow tensor)
         k = intrinsics.detach()
-        out = _ops.depth_consistency(depths.detach(), k, _ops.intrinsics_inverse_peek(k), ext.detach(), offsets, first, count, tolerance, details, sums)
+        out = _ops.depth_consistency(depths.detach(), k, _ops.intrinsics_inverse_peek(k), ext, offsets, first, count, tolerance, details, sums)
         return DepthConsistency(*out, first, offsets)
 
 
@@ -818,20 +805,8 @@ def render_views(depths: Tensor, intrinsics: Tensor, extrinsics, colors: Optiona
     they are refused."""
     what = "render_views"
     with torch.no_grad():
-        lazy = isinstance(extrinsics, LazyExtrinsics)
-        pose_tensor = extrinsics._rel if lazy else extrinsics
-        if not torch.is_tensor(depths) or not torch.is_tensor(intrinsics) or not torch.is_tensor(pose_tensor):
-            raise RuntimeError(f"flowmap_amd: {what}: depths and intrinsics must be tensors, extrinsics a tensor or a LazyExtrinsics")
-        if depths.dim() != 4:
-            raise RuntimeError(f"flowmap_amd: {what}: depths of shape {tuple(depths.shape)}; expected (batch, frame, height, width)")
+        pose_tensor = _check_posed_depths(what, depths, intrinsics, extrinsics, colors)
         b, f, h, w = depths.shape
-        if tuple(intrinsics.shape) != (b, f, 3, 3):
-            raise RuntimeError(f"flowmap_amd: {what}: intrinsics of shape {tuple(intrinsics.shape)} do not match the depths {(b, f, h, w)}: expected {(b, f, 3, 3)}")
-        if tuple(extrinsics.shape) != (b, f, 4, 4):
-            raise RuntimeError(f"flowmap_amd: {what}: extrinsics of shape {tuple(extrinsics.shape)} do not match the depths {(b, f, h, w)}: expected {(b, f, 4, 4)}")
-        if colors is not None and (not torch.is_tensor(colors) or tuple(colors.shape) != (b, f, 3, h, w)):
-            raise RuntimeError(f"flowmap_amd: {what}: colors of shape {tuple(getattr(colors, 'shape', ()))} do not match the depths {(b, f, h, w)}: "
-                               f"expected {(b, f, 3, h, w)}")
         if (views is None) == (held_out is None):
             raise ValueError(f"flowmap_amd: {what}: give exactly one of views=(K_v, E_v) and held_out=<a window of frames>")
         tensors = [("depths", depths), ("intrinsics", intrinsics), ("extrinsics", pose_tensor)] + ([("colors", colors)] if colors is not None else [])
@@ -854,9 +829,7 @@ def render_views(depths: Tensor, intrinsics: Tensor, extrinsics, colors: Optiona
             first_frame, n_views = parse_window(held_out, f, what, "frames")
             pairs = [(v, first_frame + v + d) for v in range(n_views) for d in kept_offsets if 0 <= first_frame + v + d < f]
             view_k = view_ext = None
-        for name, value in tensors:
-            if value.dtype != torch.float32:
-                raise RuntimeError(f"flowmap_amd: {what}: {name} must be float32 (got {value.dtype})")
+        _check_float32(what, tensors)
         is_int = lambda x: isinstance(x, int) and not isinstance(x, bool)  # noqa: E731
         if shape is None:
             shape = (h, w)
@@ -881,7 +854,7 @@ def render_views(depths: Tensor, intrinsics: Tensor, extrinsics, colors: Optiona
         held = slice(first_frame, first_frame + n_views) if views is None else None
         if _reference.twins and _reference.on_host(depths):  # host tensors after install(): the reference's own functions
             _reference.counters["host_calls"] += 1
-            ext = extrinsics.materialize().detach() if lazy else extrinsics.detach()
+            ext = _dense_extrinsics(extrinsics).detach()
             if views is None:
                 view_k, view_ext = intrinsics[:, held], ext[:, held]
             out = _render_on_host(_reference.twins.__getitem__, depths.detach(), intrinsics.detach(), ext, None if colors is None else colors.detach(),
@@ -889,10 +862,8 @@ def render_views(depths: Tensor, intrinsics: Tensor, extrinsics, colors: Optiona
             return RenderedViews(*out, (h, w), first_frame, kept_offsets)
         _refuse_host(what, dev)
         check_device(*(value for _, value in tensors))
-        ext = extrinsics
-        if lazy:  # the chain for this call only: nothing is kept on the LazyExtrinsics or noted on the flow tensor
-            ext = ext._dense if ext._dense is not None else _ops.PoseChain.apply(ext._rel.detach())
-        ext, k = ext.detach(), intrinsics.detach()
+        # (a LazyExtrinsics: the chain for this call only, nothing kept on it or noted on the flow tensor)
+        ext, k = _peek_extrinsics(extrinsics), intrinsics.detach()
         if views is None:
             view_k, view_ext = k[:, held], ext[:, held]
         pair_tensor = torch.tensor(pairs, dtype=torch.int32).reshape(-1, 2).to(dev)
@@ -930,10 +901,9 @@ def focal_sweep(depths: Tensor, weights, backward_flow: Tensor, focal_length_can
                                f"{(b, f, h, w)}: expected {(b, f - 1, h, w)}")
         if focal_length_candidates.dim() != 1 or focal_length_candidates.numel() < 1:
             raise RuntimeError(f"flowmap_amd: focal_sweep: focal_length_candidates must be a non-empty 1-D tensor (got shape {tuple(focal_length_candidates.shape)})")
-        for name, value in (("depths", depths), ("backward_flow", backward_flow), ("focal_length_candidates", focal_length_candidates),
-                            ("weights", weights.logits if isinstance(weights, LazyWeights) else weights)):
-            if value.dtype != torch.float32:
-                raise RuntimeError(f"flowmap_amd: focal_sweep: {name} must be float32 (got {value.dtype})")
+        weights, sens = _peek_weights(weights)
+        _check_float32("focal_sweep", (("depths", depths), ("backward_flow", backward_flow), ("focal_length_candidates", focal_length_candidates),
+                                       ("weights", weights)))
         _check_indices("focal_sweep", indices, dev)
         first, count = parse_window(pairs, f - 1, "focal_sweep", "pairs")
         if b * count > 65535:
@@ -941,7 +911,6 @@ def focal_sweep(depths: Tensor, weights, backward_flow: Tensor, focal_length_can
                              "ask for a window of pairs")
         if indices is None:
             indices = _ops.random_subset(h * w, min(h * w if num_points is None else int(num_points), h * w), dev, seed=int(seed))
-        weights, sens = _peek_weights(weights)
         from .model import focal_lengths_to_intrinsics
 
         candidates = focal_length_candidates.detach()
@@ -962,11 +931,8 @@ def _align_surfaces(surfaces, backward_flows: Tensor, backward_weights: Tensor, 
     if idx is not None and idx.numel() == h * w and getattr(idx, "_fm_is_arange", False):
         idx = None  # dense: the kernel derives the index from the thread id
     sens = 0.0
-    if isinstance(backward_weights, LazyWeights):
-        if backward_weights.sensitivity != 0.0:
-            backward_weights, sens = backward_weights.logits, backward_weights.sensitivity
-        else:
-            backward_weights = backward_weights.materialize()
+    if isinstance(backward_weights, LazyWeights):  # (at sensitivity 0 the value, evaluated and kept: the step differentiates through it)
+        backward_weights, sens = backward_weights.kernel_input(keep=True)
     if isinstance(surfaces, LazySurfaces):
         # the chain only when something reads it (LazyExtrinsics): a training step (gradients recorded) on lazy surfaces, in an optimisation
         # where nothing has asked for the extrinsics so far.  (Inside a hipGraph capture too: a reader inside the captured region becomes part of
