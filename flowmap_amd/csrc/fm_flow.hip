@@ -46,6 +46,11 @@ struct FlowParams {
   int kind;
   float delta, ax, ay;
   int iters;              // items per thread
+  // the quad loop's coordinates without a division (flow_loss_launch): a thread's item advances by the workgroup's 256 threads per
+  // iteration, so its (row, item in the row) advance by (walk_div, walk_mod) = (256 / items_per_row, 256 % items_per_row) with one carry;
+  // the pixel centres come from the host's reciprocals (pixel_center_recip, fm_math.h) in the instances the launcher picks for its range
+  int walk_div, walk_mod;
+  float inv_w, inv_h;     // 1.0f / (float)width, 1.0f / (float)height
   // fm_flow_loss_fused_adam: the Adam update of `depth` applied by this very pass (depth, exp_avg, exp_avg_sq rewritten
   // in place) for every pixel whose bit in `touched` is clear; the others keep their values and get dL/ddepth written
   float* depth_rw;        // = depth
@@ -345,7 +350,9 @@ constexpr bool kScalarTermsBits = false;
 constexpr bool kScalarTermsBits = true;
 #endif
 
-template <int VEC, int KIND, bool GRAD, int PACKED, bool ADAM = false, bool TAPS = false>
+// RECIP: the pixel centres from the host's reciprocals (pixel_center_recip, fm_math.h: both dimensions within kPixelCenterRecipMax);
+// the other instance divides, as every one did before.
+template <int VEC, int KIND, bool GRAD, int PACKED, bool RECIP, bool ADAM = false, bool TAPS = false>
 __global__ void __launch_bounds__(256, (PACKED == kFmtBits && !TAPS) ? FM_FLOW_WAVES_BITS : FM_FLOW_WAVES) flow_fused_kernel(FlowParams p) {
   constexpr bool SCALAR = kScalarTermsEverywhere || (PACKED == kFmtBits && kScalarTermsBits);
   static_assert(!ADAM || (VEC == 4 && GRAD), "the in-pass Adam update runs on the 16-byte gradient path");
@@ -365,7 +372,8 @@ __global__ void __launch_bounds__(256, (PACKED == kFmtBits && !TAPS) ? FM_FLOW_W
   const int items = n / VEC;
   const int items_per_row = p.width / VEC;
 
-  for (int c = threadIdx.x; c < p.width; c += blockDim.x) u_tab[c] = pixel_center(c, p.width);
+  const float width_f = (float)p.width, height_f = (float)p.height;
+  for (int c = threadIdx.x; c < p.width; c += blockDim.x) u_tab[c] = RECIP ? pixel_center_recip(c, width_f, p.inv_w) : pixel_center(c, p.width);
   int tap_first = 0, tap_end = 0;  // the block's run of taps
   const int block_quad0 = blockIdx.x * (blockDim.x * p.iters);
   if constexpr (TAPS) {
@@ -432,11 +440,8 @@ __global__ void __launch_bounds__(256, (PACKED == kFmtBits && !TAPS) ? FM_FLOW_W
 
   // Everything after the loads of one item: coordinates, both residual terms per pixel, store.
   auto compute = [&](const float (&z)[VEC], const float (&fxf)[VEC], const float (&fyf)[VEC], const float (&mmf)[VEC],
-                     const float (&fxb)[VEC], const float (&fyb)[VEC], const float (&mmb)[VEC], int item) {
+                     const float (&fxb)[VEC], const float (&fyb)[VEC], const float (&mmb)[VEC], int item, int col0, float v) {
     float gz[VEC];
-    const int row = item / items_per_row;
-    const int col0 = (item - row * items_per_row) * VEC;
-    const float v = pixel_center(row, p.height);
     const float v_ay = v * p.ay;
     // a1·v + a2 (and b, c alike) is constant along the image row the quad lies in
     if constexpr (SCALAR) {  // the two directions one after the other in plain fp32, behind wave-uniform run-time tests
@@ -513,7 +518,7 @@ __global__ void __launch_bounds__(256, (PACKED == kFmtBits && !TAPS) ? FM_FLOW_W
     }
   };
 
-  auto compute_quad = [&](const QuadIn& q, int item) {
+  auto compute_quad = [&](const QuadIn& q, int item, int col0, float v) {
     float z[VEC], fxf[VEC], fyf[VEC], mmf[VEC], fxb[VEC], fyb[VEC], mmb[VEC];
     if (VEC == 4) {
       z[0] = q.z.x; z[1 % VEC] = q.z.y; z[2 % VEC] = q.z.z; z[3 % VEC] = q.z.w;
@@ -524,7 +529,7 @@ __global__ void __launch_bounds__(256, (PACKED == kFmtBits && !TAPS) ? FM_FLOW_W
       fxb[0] = q.ba.x; fyb[0] = q.ba.y; fxb[1 % VEC] = q.ba.z; fyb[1 % VEC] = q.ba.w;
       fxb[2 % VEC] = q.bc.x; fyb[2 % VEC] = q.bc.y; fxb[3 % VEC] = q.bc.z; fyb[3 % VEC] = q.bc.w;
     }
-    compute(z, fxf, fyf, mmf, fxb, fyb, mmb, item);
+    compute(z, fxf, fyf, mmf, fxb, fyb, mmb, item, col0, v);
   };
 
   // (A depth-2 software pipeline of the loads — two QuadIn register sets, loop unrolled by
@@ -557,16 +562,22 @@ __global__ void __launch_bounds__(256, (PACKED == kFmtBits && !TAPS) ? FM_FLOW_W
       __syncthreads();
     }
   }
+  // (row, item in the row) are divided out once per thread and then walked with the launcher's two steps: exact for every items_per_row.
+  int row = (base + (int)threadIdx.x) / items_per_row;
+  int col = (base + (int)threadIdx.x) - row * items_per_row;
   for (int it = 0; it < p.iters; ++it) {
     const int item = base + it * blockDim.x + threadIdx.x;
     if (item >= items) break;
+    const int col0 = col * VEC;
+    const float v = RECIP ? pixel_center_recip(row, height_f, p.inv_h) : pixel_center(row, p.height);
+    item_walk(row, col, items_per_row, p.walk_div, p.walk_mod);  // (the next iteration's)
     if (VEC == 4) {
       QuadIn q = {};
       if (TAPS && it == 0) q = q_first;
       else if constexpr (PACKED == kFmtBits) load_quad_bits(q, depth, packed_bits, item, has_fwd, has_bwd);
       else if constexpr (PACKED == kFmtF32) load_quad_packed(q, depth, packed, item, has_fwd, has_bwd);
       else load_quad(q, depth, ff, mf, fb, mb, item, has_fwd, has_bwd);
-      compute_quad(q, item);
+      compute_quad(q, item, col0, v);
       continue;
     }
     float z[VEC], fxf[VEC] = {}, fyf[VEC] = {}, mmf[VEC] = {}, fxb[VEC] = {}, fyb[VEC] = {}, mmb[VEC] = {};  // (an absent direction: zeros)
@@ -596,7 +607,7 @@ __global__ void __launch_bounds__(256, (PACKED == kFmtBits && !TAPS) ? FM_FLOW_W
         fxb[0] = a.x; fyb[0] = a.y; mmb[0] = mb[item];
       }
     }
-    compute(z, fxf, fyf, mmf, fxb, fyb, mmb, item);
+    compute(z, fxf, fyf, mmf, fxb, fyb, mmb, item, col0, v);
   }
 
   if constexpr (TAPS) {
@@ -838,6 +849,9 @@ static int flow_loss_launch(const float* depth, const float* k, const float* kin
   const bool grad = scale != nullptr;
   FlowParams p{depth, k, kinv, t_fwd, t_bwd, flow_fwd, flow_bwd, mask_fwd, mask_bwd, packed, scale, grad_depth, acc,
                frames, height, width, mapping_kind, delta, aspect_x, aspect_y, items_per_thread > 0 ? items_per_thread : 4};
+  p.inv_w = 1.0f / (float)width;
+  p.inv_h = 1.0f / (float)height;
+  const bool recip = width <= kPixelCenterRecipMax && height <= kPixelCenterRecipMax;  // (else the instances that divide, as all did before)
   // element strides of the five image stacks (dense unless the caller described a view)
   FM_CHECK_ARG(flow_strides(layouts, batch, frames, (long)height * width, p.fs, p.bs));
   if (adam) {
@@ -888,28 +902,36 @@ static int flow_loss_launch(const float* depth, const float* k, const float* kin
         break;
       }
   }
+  const int items_per_row = width / vec;
+  p.walk_div = threads / items_per_row;
+  p.walk_mod = threads % items_per_row;
   const long per_block = (long)threads * p.iters;
   dim3 grid((unsigned)((items + per_block - 1) / per_block), (unsigned)(batch * frames));
   FM_CHECK_ARG(!taps || p.iters <= 6);  // (the two LDS images of a workgroup's pixels: 2 x 4 KB per quad per thread)
   size_t lds = sizeof(float) * (size_t)width + sizeof(double) * (threads / 64) * kFlowAcc;
   if (taps) lds = sizeof(float) * (size_t)((width + 3) & ~3) + sizeof(double) * (threads / 64) * kFlowAcc + 2 * sizeof(float) * 4 * (size_t)threads * p.iters;
-#define FM_FLOW_LAUNCH(V, K, P)                                                                              \
+#define FM_FLOW_LAUNCH(V, K, P, R)                                                                           \
   do {                                                                                                       \
     if (taps) {                                                                                              \
       if constexpr (V == 4) {                                                                                \
-        if (adam) hipLaunchKernelGGL((flow_fused_kernel<4, K, true, P, true, true>), grid, dim3(threads), lds, st, p);  \
-        else hipLaunchKernelGGL((flow_fused_kernel<4, K, true, P, false, true>), grid, dim3(threads), lds, st, p);      \
+        if (adam) hipLaunchKernelGGL((flow_fused_kernel<4, K, true, P, R, true, true>), grid, dim3(threads), lds, st, p);  \
+        else hipLaunchKernelGGL((flow_fused_kernel<4, K, true, P, R, false, true>), grid, dim3(threads), lds, st, p);      \
       }                                                                                                      \
     } else if (adam) {                                                                                       \
-      if constexpr (V == 4) hipLaunchKernelGGL((flow_fused_kernel<4, K, true, P, true>), grid, dim3(threads), lds, st, p); \
-    } else if (grad) hipLaunchKernelGGL((flow_fused_kernel<V, K, true, P>), grid, dim3(threads), lds, st, p);  \
-    else hipLaunchKernelGGL((flow_fused_kernel<V, K, false, P>), grid, dim3(threads), lds, st, p);          \
+      if constexpr (V == 4) hipLaunchKernelGGL((flow_fused_kernel<4, K, true, P, R, true>), grid, dim3(threads), lds, st, p); \
+    } else if (grad) hipLaunchKernelGGL((flow_fused_kernel<V, K, true, P, R>), grid, dim3(threads), lds, st, p);  \
+    else hipLaunchKernelGGL((flow_fused_kernel<V, K, false, P, R>), grid, dim3(threads), lds, st, p);        \
+  } while (0)
+#define FM_FLOW_RECIP(V, K, P)               \
+  do {                                       \
+    if (recip) FM_FLOW_LAUNCH(V, K, P, true); \
+    else FM_FLOW_LAUNCH(V, K, P, false);     \
   } while (0)
 #define FM_FLOW_KIND(V, P)                                          \
   do {                                                              \
-    if (mapping_kind == kHuber) FM_FLOW_LAUNCH(V, kHuber, P);       \
-    else if (mapping_kind == kL1) FM_FLOW_LAUNCH(V, kL1, P);        \
-    else FM_FLOW_LAUNCH(V, kL2, P);                                 \
+    if (mapping_kind == kHuber) FM_FLOW_RECIP(V, kHuber, P);        \
+    else if (mapping_kind == kL1) FM_FLOW_RECIP(V, kL1, P);         \
+    else FM_FLOW_RECIP(V, kL2, P);                                  \
   } while (0)
 #define FM_FLOW_VEC(V)                 \
   do {                                 \
@@ -932,6 +954,7 @@ static int flow_loss_launch(const float* depth, const float* k, const float* kin
   else FM_FLOW_KIND(1, kFmtNone);
 #undef FM_FLOW_VEC
 #undef FM_FLOW_KIND
+#undef FM_FLOW_RECIP
 #undef FM_FLOW_LAUNCH
   FM_LAUNCH_STATUS();
 }

@@ -57,6 +57,28 @@ FM_HD void load_pose44(const float* p, Pose& o) {
 // (int + 0.5) / length in fp32 with a true division.
 FM_HD float pixel_center(int i, int n) { return ((float)i + 0.5f) / (float)n; }
 
+// The same quotient without a division, for a caller that holds n = (float)length and inv_n = 1.0f / n (correctly rounded: computed on the
+// host): the reciprocal quotient followed by one correction step (Markstein).  For every length 1 <= n <= kPixelCenterRecipMax and every
+// 0 <= i < n it returns the BITS of pixel_center(i, n) — checked exhaustively by tests/host_checks/pixel_center_exact.cpp; beyond that
+// range nothing is claimed, and the callers divide.  The fused operations are spelled out: no contraction setting re-rounds them.
+constexpr int kPixelCenterRecipMax = 16384;
+FM_HD float pixel_center_recip(int i, float n, float inv_n) {
+  const float a = (float)i + 0.5f;
+  const float q0 = a * inv_n;
+  const float r = fmaf(-q0, n, a);
+  return fmaf(r, inv_n, q0);
+}
+
+// (row, item in the row) of an item that lies `step` items further, step_div = step / items_per_row and step_mod = step % items_per_row
+// computed once by the caller: integer adds and one carry instead of a division per item.  Exact for every items_per_row >= 1 (where
+// items_per_row < step, step_div carries the whole rows).
+FM_HD void item_walk(int& row, int& col, int items_per_row, int step_div, int step_mod) {
+  col += step_mod;
+  const bool carry = col >= items_per_row;
+  col -= carry ? items_per_row : 0;
+  row += step_div + (carry ? 1 : 0);
+}
+
 // ray = Kinv · [u, v, 1]   (projection.py:84-87)
 FM_HD void ray_dir(const Mat3& kinv, float u, float v, float ray[3]) {
   ray[0] = kinv.m[0] * u + kinv.m[1] * v + kinv.m[2];
